@@ -22,6 +22,16 @@ value = all ranks' FASTQ bytes of the timed steps / max-over-ranks time.
 `--dry-run` runs the same launcher, sharding and gather on a tiny workload with
 the CPU restatement as the encoder (no GPU; tests/test_shard.py).
 
+A plain run does what the headline needs and no more: the batches generated,
+parsed and made resident, the contexts warmed, the timed steps, the result
+line (its ratio, stream sizes and checksum from the last timed step's outputs).
+`--full` adds everything else: the outputs checked against the CPU restatement
+and against context 0 alone, the CPU baselines, and the staged-text,
+end-to-end, gzip, ingest, SE, ONT and HASH legs.  `--dump-outputs DIR` writes
+the last timed step's encoded blocks (sizes, digests, a fixed sample of the
+bytes) as .npy arrays; the inputs are seeded, so two builds run with the same
+arguments can be compared array for array.
+
 Prints one JSON line (rank 0).
 """
 from __future__ import annotations
@@ -109,8 +119,17 @@ def parse_args(argv=None):
                          "profiled bench, whose process must not start generator processes under the profiler")
     ap.add_argument("--inputs", default=None, metavar="DIR",
                     help="read the batches from FASTQ files written by --write-inputs (no generator processes)")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beside the headline too: the oracle and shared-front checks of the outputs, the "
+                         "CPU baselines, and the staged-text / end-to-end / gzip / ingest / SE / ONT / HASH legs "
+                         "(without it: set up, warm up, the timed steps, one result line)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write what the last timed step computed (its encoded blocks, as its caller fetches them) to "
+                         "DIR/<name>.npy: block_sizes and block_digests (float64, every block) and bytes_sample "
+                         "(float32, the bytes at fixed seeded positions of the concatenated blocks)")
     ap.add_argument("--no-legs", action="store_true",
-                    help="only the in-HBM line (no e2e / gzip / ingest / ONT / HASH legs, no CPU baselines)")
+                    help="with --full: only the in-HBM line and its checks (no e2e / gzip / ingest / ONT / HASH legs, "
+                         "no CPU baselines)")
     ap.add_argument("--ont-leg", type=int, default=1, help="configs[4] leg: ONT-shape SE long reads, -l 1.15 (0: skip)")
     ap.add_argument("--ont-reads", type=int, default=60_000, help="reads of the ONT leg's batch (10-50 kbp)")
     ap.add_argument("--se-leg", type=int, default=1,
@@ -151,6 +170,8 @@ def parse_args(argv=None):
         a.batches = 4 if int(os.environ.get("WORLD_SIZE", "1")) == 1 and a.gpus == 1 else 2
     if a.e2e_batches < 0:   # (N ranks: rank 0's first batch, N x 2 times over, one seqarc_amd --devices N run)
         a.e2e_batches = a.batches if int(os.environ.get("WORLD_SIZE", "1")) == 1 and a.gpus == 1 else 1
+    if not a.full:   # a plain run: the headline line alone
+        a.no_legs, a.no_verify, a.text_leg = True, True, 0
     if a.no_legs:
         a.e2e_batches, a.cpu_seconds, a.ont_leg, a.hash_leg, a.ingest_devices, a.se_leg = 0, 0.0, 0, 0, 0, 0
     if a.dry_run:
@@ -229,12 +250,97 @@ def batch_text(gid: int, args, workers: int):
                           x_span=args.x_span)
 
 
-def make_batch(gid: int, args, workers: int, files=None, texts=None):
+def _chunk_to_files(job):
+    """In a generator process: one chunk of a batch (synth._chunk), its r1 / r2
+    text written to the files `stem`_1 / `stem`_2.  Returns the two sizes."""
+    import synth
+    stem, chunk_args = job
+    sizes = []
+    for k, t in enumerate(synth._chunk(chunk_args)):
+        if t is not None:
+            with open(f"{stem}_{k + 1}", "wb") as f:
+                f.write(t)
+        sizes.append(0 if t is None else len(t))
+    return sizes
+
+
+def batch_texts(gids, args, workers: int):
+    """batch_text() of each batch of `gids`, in turn.  The generator's batches
+    are drawn chunk by chunk by one pool of processes over all of them (a chunk's
+    bytes depend on its seed and index alone, so the text is batch_text()'s):
+    the pool draws the next batches while the caller works on this one, and the
+    chunks come back as files in memory (args.e2e_dir), read on host threads,
+    where a pipe to this process carried a few hundred MB/s."""
+    import multiprocessing as mp
+    import tempfile
+    from concurrent.futures import ThreadPoolExecutor
+    import synth
+    chunks = [] if args.inputs or args.ont or workers < 2 else \
+        [synth.chunk_jobs(args.pairs, read_len=args.read_len, paired=not args.se, seed=1000 + g, x_span=args.x_span)
+         for g in gids]
+    if max(map(len, chunks), default=0) < 2:   # (one-chunk batches: drawn in this process, as generate() does)
+        for g in gids:
+            yield batch_text(g, args, workers)
+        return
+    with tempfile.TemporaryDirectory(prefix="seqarc_gen_", dir=args.e2e_dir) as d:
+        per = [len(cj) for cj in chunks]
+        jobs = [(os.path.join(d, f"b{g}_c{j[1]}"), j) for g, cj in zip(gids, chunks) for j in cj]
+
+        def read_into(dst, path, off, n):
+            with open(path, "rb") as f:
+                got = f.readinto(memoryview(dst)[off:off + n])
+            os.remove(path)
+            if got != n:
+                raise RuntimeError(f"{path}: {got} of {n} bytes")
+
+        with mp.get_context("spawn").Pool(min(workers, len(jobs))) as pool, ThreadPoolExecutor(workers) as ex:
+            res = pool.imap(_chunk_to_files, jobs)
+            at = 0
+            for n in per:
+                sizes = [next(res) for _ in range(n)]
+                texts = []
+                for k in range(1 if args.se else 2):
+                    dst = bytearray(sum(s[k] for s in sizes))
+                    off, reads = 0, []
+                    for (stem, _), s in zip(jobs[at:at + n], sizes):
+                        reads.append(ex.submit(read_into, dst, f"{stem}_{k + 1}", off, s[k]))
+                        off += s[k]
+                    for r in reads:
+                        r.result()
+                    texts.append(dst)
+                at += n
+                yield texts[0], (texts[1] if len(texts) > 1 else None)
+
+
+def cut_and_parse(t1, t2, block_size: int, threads: int):
+    """fastqueeze_amd.blocks_from_fastq (the reference reader's cut, then the
+    parse of each block) with the blocks parsed on host threads."""
+    from concurrent.futures import ThreadPoolExecutor
+    import numpy as np
+    import fastqueeze_amd as fq
+    fq.load_library()
+    a = np.frombuffer(t1, np.uint8)
+    b = None if t2 is None else np.frombuffer(t2, np.uint8)
+
+    def one(c):
+        if b is None:
+            return fq.parse_se(a[c[0]:c[1]])
+        (s1, e1), (s2, e2) = c
+        blk = fq.parse_pe(a[s1:e1], b[s2:e2])
+        blk.text1, blk.text2 = e1 - s1, e2 - s2
+        return blk
+
+    cuts = fq.cut_se(a, block_size) if b is None else fq.cut_pe(a, b, block_size)
+    with ThreadPoolExecutor(max(1, threads)) as ex:
+        return list(ex.map(one, cuts))
+
+
+def make_batch(gid: int, args, workers: int, files=None, texts=None, text=None):
     """Global batch `gid`, cut and parsed as the reference's reader does.
     Returns the parsed blocks; `files` (paths) get the FASTQ text appended (the
-    end-to-end run's input), `texts` (a list) the text itself."""
-    import fastqueeze_amd as fq
-    t1, t2 = batch_text(gid, args, workers)
+    end-to-end run's input), `texts` (a list) the text itself.  `text`: the
+    batch's (r1, r2) where the caller has it already (batch_texts)."""
+    t1, t2 = text or batch_text(gid, args, workers)
     if texts is not None:
         texts.append((t1, t2))
     if files:
@@ -242,7 +348,7 @@ def make_batch(gid: int, args, workers: int, files=None, texts=None):
             if t is not None:
                 with open(path, "ab") as f:
                     f.write(t)
-    return fq.blocks_from_fastq(t1, t2, args.block_size)
+    return cut_and_parse(t1, t2, args.block_size, workers)
 
 
 def end_to_end(args, files, contexts, expect: bytes, batch: int, threads: int, devices: int = 1,
@@ -607,6 +713,35 @@ def replicate(files, times: int):
                         left -= len(chunk)
 
 
+DUMP_SAMPLE = 4 << 20   # --dump-outputs: bytes sampled from the concatenated blocks (16 MB as float32)
+
+
+def dump_outputs(d: str, outs: list[bytes], digs: list[bytes], rank: int, world: int):
+    """--dump-outputs: the encoded blocks of one batch encode (`digs`: their
+    SHA-256s) as arrays.  block_sizes: each block's bytes; block_digests: the
+    first 30 bytes of each block's SHA-256 as five 48-bit integers (exact in
+    float64); bytes_sample: the concatenated blocks' bytes at DUMP_SAMPLE
+    positions drawn once from a fixed seed (all of them, in order, if there
+    are no more)."""
+    import numpy as np
+    os.makedirs(d, exist_ok=True)
+    sizes = np.array([len(o) for o in outs], np.float64)
+    digests = np.array([[int.from_bytes(g[6 * k:6 * k + 6], "big") for k in range(5)] for g in digs],
+                       np.float64).reshape(len(outs), 5)
+    total = int(sizes.sum())
+    starts = np.concatenate(([0], np.cumsum(sizes[:-1]))).astype(np.int64)
+    at = np.arange(total) if total <= DUMP_SAMPLE else \
+        np.sort(np.random.default_rng(2024).integers(0, total, DUMP_SAMPLE))
+    blk = np.searchsorted(starts, at, side="right") - 1
+    sample = np.empty(at.size, np.float32)
+    for i, o in enumerate(outs):
+        m = blk == i
+        sample[m] = np.frombuffer(o, np.uint8)[at[m] - starts[i]]
+    tag = "" if world == 1 else f"_rank{rank}"
+    for name, arr in (("block_sizes", sizes), ("block_digests", digests), ("bytes_sample", sample)):
+        np.save(os.path.join(d, f"{name}{tag}.npy"), arr)
+
+
 def stream_sizes(block: bytes) -> dict:
     """Payload bytes of each encap of one encoded block (doFqzEncode@0x42d2d0 layout)."""
     def vint(i):
@@ -732,6 +867,7 @@ class Workers:
         self.encs, self.inputs, self.cfg, self.gap_s = encoders, inputs, cfg, gap_s
         self.step = runner or (lambda enc, inp, c: enc.run_input(inp, c))
         self.phases, self.restarts, self.stats = [], 0, (0, 0)
+        self.last = None   # (context, input index) of the last recorded step
 
     def warm_all(self):
         """Every context encodes every batch once (its buffers reach the size of
@@ -766,6 +902,8 @@ class Workers:
                         if s >= nsteps:
                             return
                         nxt[0] += 1
+                        if record and s == nsteps - 1:   # (this context takes no step after it)
+                            self.last = (enc, s % len(self.inputs))
                     self.step(enc, self.inputs[s % len(self.inputs)], self.cfg)
                     if record and self.gap_s > 0:
                         time.sleep(self.gap_s)
@@ -871,18 +1009,18 @@ def main():
         return
     # ---- this rank's batches (global ids dealt round robin) ----
     gids = shard_indices(world * args.batches, rank, world)
-    t0 = time.time()
+    t_run = time.time()
     if args.write_inputs:   # (no GPU call in this mode)
         os.makedirs(args.write_inputs, exist_ok=True)
         for g in gids:
             for p, t in zip(input_paths(args.write_inputs, g, args.se), batch_text(g, args, workers)):
                 with open(p, "wb") as f:
                     f.write(t)
-            log(f"[rank {rank}] batch {g} written to {args.write_inputs} ({time.time() - t0:.1f}s)")
+            log(f"[rank {rank}] batch {g} written to {args.write_inputs} ({time.time() - t_run:.1f}s)")
         with open(os.path.join(args.write_inputs, "meta.json"), "w") as f:
             json.dump({k: getattr(args, k) for k in INPUT_KEYS}, f)
         return
-    batches = []
+    batches, inputs = [], []
     e2e_files = None
     if args.e2e_batches > 0 and rank == 0:
         d = os.path.join(args.e2e_dir, f"seqarc_bench_{os.getpid()}")
@@ -894,11 +1032,13 @@ def main():
         for f in e2e_files:
             open(f, "wb").close()
     texts = [] if args.text_leg and rank == 0 and world == 1 else None
-    for k, g in enumerate(gids):
+    for k, (g, text) in enumerate(zip(gids, batch_texts(gids, args, workers))):
         batches.append(make_batch(g, args, workers, e2e_files if e2e_files and k < args.e2e_batches else None,
-                                  texts))
+                                  texts, text))
+        if not args.dry_run:   # (resident while the generator's processes draw the next batch)
+            inputs.append(fq.Input(batches[-1], local))
         log(f"[rank {rank}] batch {g}: {len(batches[-1])} blocks, "
-            f"{sum(b.text_bytes for b in batches[-1]) / 1e9:.2f} GB ({time.time() - t0:.1f}s)")
+            f"{sum(b.text_bytes for b in batches[-1]) / 1e9:.2f} GB ({time.time() - t_run:.1f}s)")
     tmpl = fq.analyze_ids(batches[0][0], args.se)
     cfg = fq.Config(slevel=args.slevel, qlevel=args.qlevel, bin_mode=int(tmpl[0]), lossy=args.lossy)
     batch_bytes = [sum(b.text_bytes for b in bl) for bl in batches]
@@ -927,7 +1067,6 @@ def main():
 
     # ---- resident inputs, encoder contexts ----
     keep = {"verify": batches[0], "cpu": batches[0], "last": batches[-1]}
-    inputs = [fq.Input(bl, local) for bl in batches]
     del batches
     encs = [fq.Encoder(local)]
     for _ in range(args.contexts - 1):   # one front scratch per GPU, fronts one at a time
@@ -935,7 +1074,9 @@ def main():
     for e in encs:
         e.set_timing(True)
     W = Workers(encs, inputs, cfg, gap_s=args.step_gap_ms / 1e3)
+    log(f"[rank {rank}] inputs resident, {len(encs)} contexts ({time.time() - t_run:.1f}s)")
     W.warm_all()
+    log(f"[rank {rank}] contexts warm ({time.time() - t_run:.1f}s)")
     W.run(args.warmup, record=False)
     barrier()
     torch.cuda.synchronize(local)
@@ -944,6 +1085,7 @@ def main():
     torch.cuda.synchronize(local)
     barrier()
     elapsed = time.perf_counter() - ts
+    log(f"[rank {rank}] {args.steps} timed steps done ({time.time() - t_run:.1f}s)")
     step_bytes = sum(inputs[s % len(inputs)].text_bytes for s in range(args.steps))
     if world > 1:
         t = torch.tensor([elapsed, float(step_bytes)], dtype=torch.float64)
@@ -954,10 +1096,21 @@ def main():
     else:
         total_bytes = float(step_bytes)
 
-    # ---- outputs of batch 0: spot-check against the oracle, stream sizes,
-    #      checksum of the block checksums over all ranks ----
-    encs[0].run_input(inputs[0], cfg)
-    outs = encs[0].fetch()
+    # ---- the last timed step's outputs, fetched from the context that ran it ----
+    last_enc, ob = W.last
+    outs = last_enc.fetch() if args.dump_outputs or not args.full else None
+    sums = None if outs is None else [hashlib.sha256(o).digest() for o in outs]
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, outs, sums, rank, world)
+        log(f"[rank {rank}] outputs of batch {ob} written to {args.dump_outputs} ({time.time() - t_run:.1f}s)")
+    # ---- outputs of one batch (--full: batch 0 once more, spot-checked against
+    #      the oracle; otherwise the last step's): stream sizes, checksum of the
+    #      block checksums over all ranks ----
+    if args.full:
+        ob = 0
+        encs[0].run_input(inputs[0], cfg)
+        outs = encs[0].fetch()
+        sums = [hashlib.sha256(o).digest() for o in outs]
     out_bytes = sum(len(o) for o in outs)
     vb = keep["verify"]
     if not args.no_verify and rank == 0:
@@ -987,7 +1140,7 @@ def main():
         log(f"[rank {rank}] shared-front outputs of every batch identical to context 0 alone "
             f"(batch -> context {who}); last block of batch {len(inputs) - 1} bit-identical to the oracle")
     del keep["last"]
-    digest = hashlib.sha256(b"".join(hashlib.sha256(o).digest() for o in outs)).digest()
+    digest = hashlib.sha256(b"".join(sums)).digest()
     if world > 1:
         digs = gather_blocks([(rank, digest)], world)
     else:
@@ -998,7 +1151,7 @@ def main():
     ph = {k: float(np.median([p[k] for p in W.phases])) for k in W.phases[0]}
     kern = {k: v for k, v in ph.items() if k != "total"}
     dom = max(kern, key=kern.get)
-    in0 = inputs[0].text_bytes
+    in0 = inputs[ob].text_bytes
     algo_bytes = in0 + out_bytes          # FASTQ in + encoded out, per launch (one batch)
     achieved = algo_bytes / (kern[dom] / 1e3) / 1e9
     traffic = None
@@ -1072,6 +1225,7 @@ def main():
                    "contexts_per_gpu": args.contexts, "batches_per_gpu": args.batches,
                    "parallelism": f"block-shard x{world} (batches dealt by shard_indices)"},
         "ratio": round(in0 / out_bytes, 3),
+        "outputs_of_batch": ob,   # ratio, streams_block0 and checksum are of this resident batch's encode
         "streams_block0": streams,
         "streams_survey_ref": SURVEY_STREAMS,
         "roofline": {"bound": "hbm", "kernel": dom, "achieved": round(achieved, 2), "peak": HBM_PEAK_GBS,
@@ -1218,6 +1372,7 @@ def main():
                                                                                   "fastq_bytes",
                                                                                   "e2e_roundtrip_md5_ok")}
     barrier()
+    log(f"[rank {rank}] done ({time.time() - t_run:.1f}s)")
     if rank == 0:
         print(json.dumps(res), flush=True)
     if world > 1:

@@ -20,4 +20,4 @@ step smoke timeout -k 10 300 python -u -c "import __graft_entry__ as g; g.smoke(
 if [ -z "$NO_PROF" ]; then
     TAG=$TAG/prof_set step profile bash scripts/gpu_r4b.sh
 fi
-step bench timeout -k 10 1000 python -u bench.py --e2e-log $O/e2e.log ${BENCH_ARGS} > $O/bench.json 2> $O/bench.err
+step bench timeout -k 10 1000 python -u bench.py --full --e2e-log $O/e2e.log ${BENCH_ARGS} > $O/bench.json 2> $O/bench.err

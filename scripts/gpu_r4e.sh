@@ -40,7 +40,7 @@ CLI="fastqueeze_amd/bin/seqarc_amd -c -f -v -t 16 -1 $C/r1.fq -2 $C/r2.fq -o $C/
 SA_RV_PROBE=$O/probe_cli.txt run_smi cli timeout -k 10 300 $CLI > $O/cli.log 2>&1
 SA_RV_PROBE=$O/probe_cli_hostparse.txt run_smi cli_hostparse timeout -k 10 300 $CLI --host-parse > $O/cli_hostparse.log 2>&1
 rm -rf $C
-B="bench.py --inputs $IN --no-legs --no-verify --steps 24"
+B="bench.py --full --inputs $IN --no-legs --no-verify --steps 24"
 SA_RV_PROBE=$O/probe_bench.txt run_smi bench timeout -k 10 300 python -u $B > $O/bench.json 2> $O/bench.err
 python -u scripts/h2d_stress.py --gbs 10 --seconds 40 > $O/h2d_stress.log 2>&1 & H2D=$!
 SA_RV_PROBE=$O/probe_bench_h2d.txt run_smi bench_h2d timeout -k 10 300 python -u $B > $O/bench_h2d.json 2> $O/bench_h2d.err

@@ -33,7 +33,7 @@ run_smi() {
     sleep 8
 }
 step write_inputs timeout -k 10 300 python -u bench.py --write-inputs $IN > $O/write_inputs.log 2>&1
-B="bench.py --inputs $IN --no-legs --no-verify --steps 32"
+B="bench.py --full --inputs $IN --no-legs --no-verify --steps 32"
 python -u scripts/cpu_stress.py --mode mem --threads 16 --seconds 45 > $O/stress_mem.log 2>&1 & S=$!
 SA_RV_PROBE=$O/probe_bench_mem.txt run_smi bench_mem timeout -k 10 300 python -u $B > $O/bench_mem.json 2> $O/bench_mem.err
 wait $S

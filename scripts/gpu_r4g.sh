@@ -34,7 +34,7 @@ run_smi() {
 }
 step parity timeout -k 10 600 python -u -m pytest tests/test_gpu_parity.py -m gpu -x -q --timeout 120 --timeout-method thread -o cache_dir=/tmp/pyc > $O/parity.log 2>&1
 step write_inputs timeout -k 10 300 python -u bench.py --write-inputs $IN > $O/write_inputs.log 2>&1
-B="bench.py --inputs $IN --no-legs --no-verify --steps 24"
+B="bench.py --full --inputs $IN --no-legs --no-verify --steps 24"
 SA_RV_PROBE=$O/probe_gap700.txt run_smi gap700 timeout -k 10 300 python -u $B --step-gap-ms 700 > $O/gap700.json 2> $O/gap700.err
 SA_RV_PROBE=$O/probe_gap300.txt run_smi gap300 timeout -k 10 300 python -u $B --step-gap-ms 300 > $O/gap300.json 2> $O/gap300.err
 mkdir -p $C

@@ -34,7 +34,7 @@ run_smi() {
     sleep 8
 }
 step write_inputs timeout -k 10 300 python -u bench.py --write-inputs $IN > $O/write_inputs.log 2>&1
-B="bench.py --inputs $IN --no-legs --no-verify --steps 24"
+B="bench.py --full --inputs $IN --no-legs --no-verify --steps 24"
 SA_RV_PROBE=$O/probe_bench_block.txt SA_SYNC=block run_smi bench_block timeout -k 10 300 python -u $B > $O/bench_block.json 2> $O/bench_block.err
 SA_L_CU_EVERY=4 run_smi bench_l4 timeout -k 10 300 python -u $B > $O/bench_l4.json 2> $O/bench_l4.err
 SA_L_CU_EVERY=2 run_smi bench_l2 timeout -k 10 300 python -u $B > $O/bench_l2.json 2> $O/bench_l2.err

@@ -41,9 +41,9 @@ cli() {   # name, env...
     [ $rc -eq 0 ]
 }
 step write_inputs timeout -k 10 300 python -u bench.py --write-inputs $IN > $O/write_inputs.log 2>&1
-step bench_c5a timeout -k 10 300 python -u bench.py --inputs $IN --no-legs --no-verify --contexts 5 > $O/bench_c5a.json 2> $O/bench_c5a.err
-step bench_c6 timeout -k 10 300 python -u bench.py --inputs $IN --no-legs --no-verify --contexts 6 > $O/bench_c6.json 2> $O/bench_c6.err
-step bench_c5b timeout -k 10 300 python -u bench.py --inputs $IN --no-legs --no-verify --contexts 5 > $O/bench_c5b.json 2> $O/bench_c5b.err
+step bench_c5a timeout -k 10 300 python -u bench.py --full --inputs $IN --no-legs --no-verify --contexts 5 > $O/bench_c5a.json 2> $O/bench_c5a.err
+step bench_c6 timeout -k 10 300 python -u bench.py --full --inputs $IN --no-legs --no-verify --contexts 6 > $O/bench_c6.json 2> $O/bench_c6.err
+step bench_c5b timeout -k 10 300 python -u bench.py --full --inputs $IN --no-legs --no-verify --contexts 5 > $O/bench_c5b.json 2> $O/bench_c5b.err
 mkdir -p $E
 for k in 1 2 3; do for g in 0 1 2 3; do cat $IN/b${g}_r1.fq >> $E/r1.fq; cat $IN/b${g}_r2.fq >> $E/r2.fq; done; done
 rm -rf $IN

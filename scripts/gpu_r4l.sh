@@ -53,6 +53,6 @@ sleep 8
 (for i in 1 2 3 4 5 6 7 8 9 10; do (cd $E && timeout -k 5 60 $R/fastqueeze_amd/bin/seqarc_amd -c -f -t 16 -1 r1.fq -2 r2.fq -o ing --contexts 5 --batch 69 --block-size 50 --devices 8 --ingest-only) >> $O/ingest_loop.log 2>&1; rm -f $E/ing.arc; done) & BG=$!
 sleep 3
 sampler $O/smi_staged_reader.txt & SMI=$!
-SA_RV_PROBE=$O/probe_staged_reader.txt step staged_reader timeout -k 10 300 python -u bench.py --inputs $IN --no-legs --no-verify --steps 2 --warmup 0 --text-steps 30 > $O/staged_reader.json 2> $O/staged_reader.err
+SA_RV_PROBE=$O/probe_staged_reader.txt step staged_reader timeout -k 10 300 python -u bench.py --full --inputs $IN --no-legs --no-verify --steps 2 --warmup 0 --text-steps 30 > $O/staged_reader.json 2> $O/staged_reader.err
 kill $SMI $BG 2>/dev/null; wait $SMI $BG 2>/dev/null
 python3 scripts/rv_probe.py $O/probe_base.txt $O/probe_torch_beside.txt $O/probe_staged_reader.txt > $O/probe_report.txt 2>&1

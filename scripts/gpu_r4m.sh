@@ -40,7 +40,7 @@ cli() {   # name, extra args
 }
 bgap() {   # gap ms
     sampler $O/smi_gap$1.txt & SMI=$!
-    SA_RV_PROBE=$O/probe_gap$1.txt step gap$1 timeout -k 10 300 python -u bench.py --inputs $IN --no-legs --no-verify --text-leg 0 --steps 25 --step-gap-ms $1 > $O/gap$1.json 2> $O/gap$1.err
+    SA_RV_PROBE=$O/probe_gap$1.txt step gap$1 timeout -k 10 300 python -u bench.py --full --inputs $IN --no-legs --no-verify --text-leg 0 --steps 25 --step-gap-ms $1 > $O/gap$1.json 2> $O/gap$1.err
     kill $SMI 2>/dev/null; wait $SMI 2>/dev/null
 }
 step write_inputs timeout -k 10 300 python -u bench.py --write-inputs $IN > $O/write_inputs.log 2>&1

@@ -19,6 +19,6 @@ step() {
 }
 SA_L_CHUNK=16 step tests timeout -k 10 480 python -u -m pytest tests/test_gpu_parity.py -m gpu -v --timeout 120 --timeout-method thread -o cache_dir=/tmp/pyc > $O/tests.log 2>&1
 step write_inputs timeout -k 10 300 python -u bench.py --write-inputs $IN > $O/write_inputs.log 2>&1
-step bench_a timeout -k 10 300 python -u bench.py --inputs $IN --no-legs --text-leg 0 > $O/bench_a.json 2> $O/bench_a.err
-SA_L_CHUNK=16 step bench_l16 timeout -k 10 300 python -u bench.py --inputs $IN --no-legs --text-leg 0 > $O/bench_l16.json 2> $O/bench_l16.err
-step bench_b timeout -k 10 300 python -u bench.py --inputs $IN --no-legs --text-leg 0 > $O/bench_b.json 2> $O/bench_b.err
+step bench_a timeout -k 10 300 python -u bench.py --full --inputs $IN --no-legs --text-leg 0 > $O/bench_a.json 2> $O/bench_a.err
+SA_L_CHUNK=16 step bench_l16 timeout -k 10 300 python -u bench.py --full --inputs $IN --no-legs --text-leg 0 > $O/bench_l16.json 2> $O/bench_l16.err
+step bench_b timeout -k 10 300 python -u bench.py --full --inputs $IN --no-legs --text-leg 0 > $O/bench_b.json 2> $O/bench_b.err

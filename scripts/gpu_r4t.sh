@@ -10,7 +10,7 @@ export TMPDIR=/tmp SA_NO_BUILD=1
 timeout -k 10 480 python -u -m pytest tests -m gpu -v --timeout 120 --timeout-method thread -o cache_dir=/tmp/pyc > $O/tests.log 2>&1
 rc=$?; echo "tests rc=$rc" >> $O/steps.txt
 [ $rc -eq 0 ] || exit $rc
-timeout -k 10 300 python -u bench.py --no-legs --text-leg 0 > $O/bench.json 2> $O/bench.err
+timeout -k 10 300 python -u bench.py --full --no-legs --text-leg 0 > $O/bench.json 2> $O/bench.err
 rc=$?; echo "bench rc=$rc" >> $O/steps.txt
 [ $rc -eq 0 ] || exit $rc
 TAG=r4t/prof_set bash scripts/gpu_r4b.sh

@@ -18,6 +18,6 @@ step() {
     if [ $rc -ne 0 ] && [ $rc -ne 1 ]; then exit $rc; fi
 }
 step write_inputs timeout -k 10 300 python -u bench.py --write-inputs $IN > $O/write_inputs.log 2>&1
-step bench_a timeout -k 10 300 python -u bench.py --inputs $IN --no-legs --text-leg 0 > $O/bench_a.json 2> $O/bench_a.err
-SA_L_PRIO=1 step bench_lprio timeout -k 10 300 python -u bench.py --inputs $IN --no-legs --text-leg 0 > $O/bench_lprio.json 2> $O/bench_lprio.err
-step bench_b timeout -k 10 300 python -u bench.py --inputs $IN --no-legs --text-leg 0 > $O/bench_b.json 2> $O/bench_b.err
+step bench_a timeout -k 10 300 python -u bench.py --full --inputs $IN --no-legs --text-leg 0 > $O/bench_a.json 2> $O/bench_a.err
+SA_L_PRIO=1 step bench_lprio timeout -k 10 300 python -u bench.py --full --inputs $IN --no-legs --text-leg 0 > $O/bench_lprio.json 2> $O/bench_lprio.err
+step bench_b timeout -k 10 300 python -u bench.py --full --inputs $IN --no-legs --text-leg 0 > $O/bench_b.json 2> $O/bench_b.err

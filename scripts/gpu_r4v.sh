@@ -19,6 +19,6 @@ step() {
 }
 step gpu_tests timeout -k 10 900 python -u -m pytest tests -m gpu -x -v --timeout 240 --timeout-method thread > $O/gpu_tests.log 2>&1
 step write_inputs timeout -k 10 300 python -u bench.py --write-inputs $IN > $O/write_inputs.log 2>&1
-step bench_a timeout -k 10 300 python -u bench.py --inputs $IN --no-legs --text-leg 0 > $O/bench_a.json 2> $O/bench_a.err
-SA_ASYNC_TAIL=0 step bench_sync timeout -k 10 300 python -u bench.py --inputs $IN --no-legs --text-leg 0 > $O/bench_sync.json 2> $O/bench_sync.err
-step bench_b timeout -k 10 300 python -u bench.py --inputs $IN --no-legs --text-leg 0 > $O/bench_b.json 2> $O/bench_b.err
+step bench_a timeout -k 10 300 python -u bench.py --full --inputs $IN --no-legs --text-leg 0 > $O/bench_a.json 2> $O/bench_a.err
+SA_ASYNC_TAIL=0 step bench_sync timeout -k 10 300 python -u bench.py --full --inputs $IN --no-legs --text-leg 0 > $O/bench_sync.json 2> $O/bench_sync.err
+step bench_b timeout -k 10 300 python -u bench.py --full --inputs $IN --no-legs --text-leg 0 > $O/bench_b.json 2> $O/bench_b.err

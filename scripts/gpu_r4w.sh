@@ -16,5 +16,5 @@ step() {
 }
 step tests timeout -k 10 480 python -u -m pytest tests -m gpu -v --timeout 120 --timeout-method thread -o cache_dir=/tmp/pyc > $O/tests.log 2>&1
 step smoke timeout -k 10 300 python -u -c "import __graft_entry__ as g; g.smoke()" > $O/smoke.log 2>&1
-step bench timeout -k 10 660 python -u bench.py --e2e-log $O/e2e.log > $O/bench.json 2> $O/bench.err
-SA_GZ_COPY_THREADS=1 step bench_copy1 timeout -k 10 500 python -u bench.py --steps 8 --ont-leg 0 --hash-leg 0 --text-leg 0 --decode-check 0 > $O/bench_copy1.json 2> $O/bench_copy1.err
+step bench timeout -k 10 660 python -u bench.py --full --e2e-log $O/e2e.log > $O/bench.json 2> $O/bench.err
+SA_GZ_COPY_THREADS=1 step bench_copy1 timeout -k 10 500 python -u bench.py --full --steps 8 --ont-leg 0 --hash-leg 0 --text-leg 0 --decode-check 0 > $O/bench_copy1.json 2> $O/bench_copy1.err

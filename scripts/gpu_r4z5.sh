@@ -15,7 +15,7 @@ step() {
     echo "$name rc=$rc $((SECONDS - t0))s" >> $O/steps.txt
     if [ $rc -ne 0 ]; then exit $rc; fi
 }
-B="bench.py --ont --pairs 60000 --lossy 1.15 --no-legs --text-leg 0 --no-verify --steps 10"
+B="bench.py --full --ont --pairs 60000 --lossy 1.15 --no-legs --text-leg 0 --no-verify --steps 10"
 SA_RV_VARIANT=0 step ont_v0a timeout -k 10 300 python -u $B > $O/ont_v0a.json 2> $O/ont_v0a.err
 step ont_v5a timeout -k 10 300 python -u $B > $O/ont_v5a.json 2> $O/ont_v5a.err
 SA_RV_VARIANT=0 step ont_v0b timeout -k 10 300 python -u $B > $O/ont_v0b.json 2> $O/ont_v0b.err

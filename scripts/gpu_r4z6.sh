@@ -18,7 +18,7 @@ step() {
     if [ $rc -ne 0 ]; then exit $rc; fi
 }
 step write_inputs timeout -k 10 300 python -u bench.py --write-inputs $IN > $O/write_inputs.log 2>&1
-step bench_v5a timeout -k 10 300 python -u bench.py --inputs $IN --no-legs --text-leg 0 > $O/bench_v5a.json 2> $O/bench_v5a.err
-SA_RV_VARIANT=7 step bench_v7a timeout -k 10 300 python -u bench.py --inputs $IN --no-legs --text-leg 0 > $O/bench_v7a.json 2> $O/bench_v7a.err
-step bench_v5b timeout -k 10 300 python -u bench.py --inputs $IN --no-legs --text-leg 0 > $O/bench_v5b.json 2> $O/bench_v5b.err
-SA_RV_VARIANT=7 step bench_v7b timeout -k 10 300 python -u bench.py --inputs $IN --no-legs --text-leg 0 > $O/bench_v7b.json 2> $O/bench_v7b.err
+step bench_v5a timeout -k 10 300 python -u bench.py --full --inputs $IN --no-legs --text-leg 0 > $O/bench_v5a.json 2> $O/bench_v5a.err
+SA_RV_VARIANT=7 step bench_v7a timeout -k 10 300 python -u bench.py --full --inputs $IN --no-legs --text-leg 0 > $O/bench_v7a.json 2> $O/bench_v7a.err
+step bench_v5b timeout -k 10 300 python -u bench.py --full --inputs $IN --no-legs --text-leg 0 > $O/bench_v5b.json 2> $O/bench_v5b.err
+SA_RV_VARIANT=7 step bench_v7b timeout -k 10 300 python -u bench.py --full --inputs $IN --no-legs --text-leg 0 > $O/bench_v7b.json 2> $O/bench_v7b.err

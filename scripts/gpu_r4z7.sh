@@ -18,7 +18,7 @@ step() {
     if [ $rc -ne 0 ]; then exit $rc; fi
 }
 step write_inputs timeout -k 10 300 python -u bench.py --write-inputs $IN > $O/write_inputs.log 2>&1
-step bench_e4a timeout -k 10 300 python -u bench.py --inputs $IN --no-legs --text-leg 0 > $O/bench_e4a.json 2> $O/bench_e4a.err
-SA_LONG_CU_EVERY=3 step bench_e3a timeout -k 10 300 python -u bench.py --inputs $IN --no-legs --text-leg 0 > $O/bench_e3a.json 2> $O/bench_e3a.err
-step bench_e4b timeout -k 10 300 python -u bench.py --inputs $IN --no-legs --text-leg 0 > $O/bench_e4b.json 2> $O/bench_e4b.err
-SA_LONG_CU_EVERY=3 step bench_e3b timeout -k 10 300 python -u bench.py --inputs $IN --no-legs --text-leg 0 > $O/bench_e3b.json 2> $O/bench_e3b.err
+step bench_e4a timeout -k 10 300 python -u bench.py --full --inputs $IN --no-legs --text-leg 0 > $O/bench_e4a.json 2> $O/bench_e4a.err
+SA_LONG_CU_EVERY=3 step bench_e3a timeout -k 10 300 python -u bench.py --full --inputs $IN --no-legs --text-leg 0 > $O/bench_e3a.json 2> $O/bench_e3a.err
+step bench_e4b timeout -k 10 300 python -u bench.py --full --inputs $IN --no-legs --text-leg 0 > $O/bench_e4b.json 2> $O/bench_e4b.err
+SA_LONG_CU_EVERY=3 step bench_e3b timeout -k 10 300 python -u bench.py --full --inputs $IN --no-legs --text-leg 0 > $O/bench_e3b.json 2> $O/bench_e3b.err

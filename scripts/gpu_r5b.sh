@@ -33,7 +33,7 @@ step tests timeout -k 10 600 python -u -m pytest tests -m gpu -x -v --timeout 12
 step write_inputs timeout -k 10 300 python -u bench.py --write-inputs $IN > $O/write_inputs.log 2>&1
 sleep 5
 sampler $O/smi_bench.txt & SMI=$!
-SA_RV_PROBE=$O/probe_bench.txt step bench timeout -k 10 300 python -u bench.py --inputs $IN --no-legs --no-verify --steps 24 > $O/bench.json 2> $O/bench.err
+SA_RV_PROBE=$O/probe_bench.txt step bench timeout -k 10 300 python -u bench.py --full --inputs $IN --no-legs --no-verify --steps 24 > $O/bench.json 2> $O/bench.err
 kill $SMI; wait $SMI 2>/dev/null
 mkdir -p $E
 for k in 1 2 3; do for g in 0 1 2 3; do cat $IN/b${g}_r1.fq >> $E/r1.fq; cat $IN/b${g}_r2.fq >> $E/r2.fq; done; done
@@ -48,4 +48,4 @@ kill $SMI; wait $SMI 2>/dev/null
 rm -rf $E
 python3 scripts/rv_probe.py $O/probe_bench.txt $O/probe_cli.txt > $O/probe_report.txt 2>&1
 step write_ont timeout -k 10 300 python -u bench.py --write-inputs $INO --ont --lossy 1.15 --batches 1 > $O/write_ont.log 2>&1
-step ont_trace timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $O/ont_prof -o ont -- python3 -u bench.py --inputs $INO --ont --lossy 1.15 --batches 1 --no-legs --no-verify --steps 4 --warmup 1 > $O/ont.json 2> $O/ont.err
+step ont_trace timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $O/ont_prof -o ont -- python3 -u bench.py --full --inputs $INO --ont --lossy 1.15 --batches 1 --no-legs --no-verify --steps 4 --warmup 1 > $O/ont.json 2> $O/ont.err

@@ -22,13 +22,13 @@ step() {
     if [ $rc -ne 0 ]; then exit $rc; fi
 }
 python3 scripts/kfd_sample.py $O/kfd_bench.txt & KS=$!
-SA_SEQ_BUCKET=0 step bench timeout -k 10 540 python -u bench.py --e2e-log $O/e2e.log > $O/bench.json 2> $O/bench.err
+SA_SEQ_BUCKET=0 step bench timeout -k 10 540 python -u bench.py --full --e2e-log $O/e2e.log > $O/bench.json 2> $O/bench.err
 kill $KS
 step tests timeout -k 10 600 python -u -m pytest tests -m gpu -x -v --timeout 120 --timeout-method thread -o cache_dir=/tmp/pyc > $O/tests.log 2>&1
 step smoke timeout -k 10 120 python -u -c "import __graft_entry__ as g; g.smoke()" > $O/smoke.log 2>&1
 step write_inputs timeout -k 10 300 python -u bench.py --write-inputs $IN > $O/write_inputs.log 2>&1
 for v in 0 1 0 1; do
-    SA_SEQ_BUCKET=$v step ab_$v timeout -k 10 300 python -u bench.py --inputs $IN --no-legs > $O/ab_$v.json 2>> $O/ab.err
+    SA_SEQ_BUCKET=$v step ab_$v timeout -k 10 300 python -u bench.py --full --inputs $IN --no-legs > $O/ab_$v.json 2>> $O/ab.err
     cat $O/ab_$v.json >> $O/ab_all.jsonl
 done
-step solo_prof timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $O/solo_prof -o solo -- python3 -u bench.py --inputs $IN --no-legs --no-verify --contexts 1 --steps 4 --warmup 1 > $O/solo.json 2> $O/solo.err
+step solo_prof timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $O/solo_prof -o solo -- python3 -u bench.py --full --inputs $IN --no-legs --no-verify --contexts 1 --steps 4 --warmup 1 > $O/solo.json 2> $O/solo.err

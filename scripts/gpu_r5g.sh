@@ -24,9 +24,9 @@ step write_inputs timeout -k 10 300 python -u bench.py --write-inputs $IN > $O/w
 for rep in 1 2; do
     for lb in "0 0" "1 0" "0 1" "1 1"; do
         set -- $lb
-        SA_RV_LANES=$1 SA_SEQ_BUCKET=$2 step ab_l$1_b$2 timeout -k 10 300 python -u bench.py --inputs $IN --no-legs > $O/ab_l$1_b$2_$rep.json 2>> $O/ab.err
+        SA_RV_LANES=$1 SA_SEQ_BUCKET=$2 step ab_l$1_b$2 timeout -k 10 300 python -u bench.py --full --inputs $IN --no-legs > $O/ab_l$1_b$2_$rep.json 2>> $O/ab.err
         echo "{\"lanes\": $1, \"bucket\": $2, \"rep\": $rep, \"line\": $(cat $O/ab_l$1_b$2_$rep.json)}" >> $O/ab_all.jsonl
     done
 done
-SA_RV_LANES=1 step solo_prof timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $O/solo_prof -o solo -- python3 -u bench.py --inputs $IN --no-legs --no-verify --contexts 1 --steps 4 --warmup 1 > $O/solo.json 2> $O/solo.err
-SA_RV_LANES=1 step load_prof timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $O/load_prof -o load -- python3 -u bench.py --inputs $IN --no-legs --no-verify --steps 16 --warmup 2 > $O/load.json 2> $O/load.err
+SA_RV_LANES=1 step solo_prof timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $O/solo_prof -o solo -- python3 -u bench.py --full --inputs $IN --no-legs --no-verify --contexts 1 --steps 4 --warmup 1 > $O/solo.json 2> $O/solo.err
+SA_RV_LANES=1 step load_prof timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $O/load_prof -o load -- python3 -u bench.py --full --inputs $IN --no-legs --no-verify --steps 16 --warmup 2 > $O/load.json 2> $O/load.err

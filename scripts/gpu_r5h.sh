@@ -25,12 +25,12 @@ step write_inputs timeout -k 10 300 python -u bench.py --write-inputs $IN > $O/w
 for rep in 1 2; do
     for fb in "1 0" "0 0" "1 1" "0 1"; do
         set -- $fb
-        SA_FRONT_STATIC=$1 SA_SEQ_BUCKET=$2 step ab_s$1_b$2 timeout -k 10 300 python -u bench.py --inputs $IN --no-legs > $O/ab_s$1_b$2_$rep.json 2>> $O/ab.err
+        SA_FRONT_STATIC=$1 SA_SEQ_BUCKET=$2 step ab_s$1_b$2 timeout -k 10 300 python -u bench.py --full --inputs $IN --no-legs > $O/ab_s$1_b$2_$rep.json 2>> $O/ab.err
         echo "{\"static\": $1, \"bucket\": $2, \"rep\": $rep, \"line\": $(cat $O/ab_s$1_b$2_$rep.json)}" >> $O/ab_all.jsonl
     done
 done
-step solo_prof timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $O/solo_prof -o solo -- python3 -u bench.py --inputs $IN --no-legs --no-verify --contexts 1 --steps 4 --warmup 1 > $O/solo.json 2> $O/solo.err
-step load_prof timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $O/load_prof -o load -- python3 -u bench.py --inputs $IN --no-legs --no-verify --steps 16 --warmup 2 > $O/load.json 2> $O/load.err
+step solo_prof timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $O/solo_prof -o solo -- python3 -u bench.py --full --inputs $IN --no-legs --no-verify --contexts 1 --steps 4 --warmup 1 > $O/solo.json 2> $O/solo.err
+step load_prof timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $O/load_prof -o load -- python3 -u bench.py --full --inputs $IN --no-legs --no-verify --steps 16 --warmup 2 > $O/load.json 2> $O/load.err
 rm -rf $IN
 step write_ont timeout -k 10 300 python -u bench.py --write-inputs $INO --ont --lossy 1.15 --batches 1 > $O/write_ont.log 2>&1
-step ont_prof timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $O/ont_prof -o ont -- python3 -u bench.py --inputs $INO --ont --lossy 1.15 --batches 1 --no-legs --steps 6 --warmup 1 > $O/ont.json 2> $O/ont.err
+step ont_prof timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $O/ont_prof -o ont -- python3 -u bench.py --full --inputs $INO --ont --lossy 1.15 --batches 1 --no-legs --steps 6 --warmup 1 > $O/ont.json 2> $O/ont.err

@@ -22,10 +22,10 @@ step tests timeout -k 10 600 python -u -m pytest tests -m gpu -x -v --timeout 12
 step write_inputs timeout -k 10 300 python -u bench.py --write-inputs $IN > $O/write_inputs.log 2>&1
 for rep in 1 2; do
     for bk in 0 1; do
-        SA_SEQ_BUCKET=$bk step ab_b$bk timeout -k 10 300 python -u bench.py --inputs $IN --no-legs > $O/ab_b${bk}_$rep.json 2>> $O/ab.err
+        SA_SEQ_BUCKET=$bk step ab_b$bk timeout -k 10 300 python -u bench.py --full --inputs $IN --no-legs > $O/ab_b${bk}_$rep.json 2>> $O/ab.err
         echo "{\"bucket\": $bk, \"rep\": $rep, \"line\": $(cat $O/ab_b${bk}_$rep.json)}" >> $O/ab_all.jsonl
     done
 done
-SA_SEQ_BUCKET=1 step bkt_prof timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $O/bkt_prof -o bkt -- python3 -u bench.py --inputs $IN --no-legs --no-verify --contexts 1 --steps 4 --warmup 1 > $O/bkt.json 2> $O/bkt.err
+SA_SEQ_BUCKET=1 step bkt_prof timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $O/bkt_prof -o bkt -- python3 -u bench.py --full --inputs $IN --no-legs --no-verify --contexts 1 --steps 4 --warmup 1 > $O/bkt.json 2> $O/bkt.err
 rm -rf $IN
 TAG=r5i_cli step cli bash scripts/gpu_r5f.sh

@@ -29,11 +29,11 @@ step write_inputs timeout -k 10 300 python -u bench.py --write-inputs $IN > $O/w
 for rep in 1 2; do
     for lcb in "0 5 0" "1 5 0" "1 6 0" "0 5 1"; do
         set -- $lcb
-        SA_RV_LANES=$1 SA_SEQ_BUCKET=$3 step ab_l$1_c$2_b$3 timeout -k 10 300 python -u bench.py --inputs $IN --no-legs --contexts $2 > $O/ab_l$1_c$2_b$3_$rep.json 2>> $O/ab.err
+        SA_RV_LANES=$1 SA_SEQ_BUCKET=$3 step ab_l$1_c$2_b$3 timeout -k 10 300 python -u bench.py --full --inputs $IN --no-legs --contexts $2 > $O/ab_l$1_c$2_b$3_$rep.json 2>> $O/ab.err
         echo "{\"lanes\": $1, \"contexts\": $2, \"bucket\": $3, \"rep\": $rep, \"line\": $(cat $O/ab_l$1_c$2_b$3_$rep.json)}" >> $O/ab_all.jsonl
     done
 done
-SA_RV_LANES=1 step solo_prof timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $O/solo_prof -o solo -- python3 -u bench.py --inputs $IN --no-legs --no-verify --contexts 1 --steps 4 --warmup 1 > $O/solo.json 2> $O/solo.err
+SA_RV_LANES=1 step solo_prof timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $O/solo_prof -o solo -- python3 -u bench.py --full --inputs $IN --no-legs --no-verify --contexts 1 --steps 4 --warmup 1 > $O/solo.json 2> $O/solo.err
 mkdir -p $E/s $E/l
 for g in 0 1 2 3 0; do cat $IN/b${g}_r1.fq >> $E/s/r1.fq; cat $IN/b${g}_r2.fq >> $E/s/r2.fq; done
 for k in 1 2 3; do for g in 0 1 2 3; do cat $IN/b${g}_r1.fq >> $E/l/r1.fq; cat $IN/b${g}_r2.fq >> $E/l/r2.fq; done; done

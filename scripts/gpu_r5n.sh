@@ -23,7 +23,7 @@ SA_RV_LANES=1 step tests timeout -k 10 600 python -u -m pytest tests -m gpu -x -
 step write_inputs timeout -k 10 300 python -u bench.py --write-inputs $IN > $O/write_inputs.log 2>&1
 for rep in 1 2; do
     for l in 0 1; do
-        SA_RV_LANES=$l step ab_l$l timeout -k 10 300 python -u bench.py --inputs $IN --no-legs > $O/ab_l${l}_$rep.json 2>> $O/ab.err
+        SA_RV_LANES=$l step ab_l$l timeout -k 10 300 python -u bench.py --full --inputs $IN --no-legs > $O/ab_l${l}_$rep.json 2>> $O/ab.err
         echo "{\"lanes\": $l, \"rep\": $rep, \"line\": $(cat $O/ab_l${l}_$rep.json)}" >> $O/ab_all.jsonl
     done
 done

@@ -27,7 +27,7 @@ step pin_probe timeout -k 10 180 scripts/bin/pin_probe 8 > $O/pin_probe.txt 2>&1
 step write_inputs timeout -k 10 300 python -u bench.py --write-inputs $IN > $O/write_inputs.log 2>&1
 for rep in 1 2; do
     for l in 0 1; do
-        SA_RV_LANES=$l step ab_l$l timeout -k 10 300 python -u bench.py --inputs $IN --no-legs > $O/ab_l${l}_$rep.json 2>> $O/ab.err
+        SA_RV_LANES=$l step ab_l$l timeout -k 10 300 python -u bench.py --full --inputs $IN --no-legs > $O/ab_l${l}_$rep.json 2>> $O/ab.err
         echo "{\"lanes\": $l, \"rep\": $rep, \"line\": $(cat $O/ab_l${l}_$rep.json)}" >> $O/ab_all.jsonl
     done
 done

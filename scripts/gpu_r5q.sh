@@ -21,7 +21,7 @@ step write_inputs timeout -k 10 300 python -u bench.py --write-inputs $IN > $O/w
 for rep in 1 2; do
     for n in 0 5 4; do
         if [ $n = 0 ]; then ev="X=1"; else ev="SA_RV_CUS=$n"; fi
-        env $ev timeout -k 10 300 python -u bench.py --inputs $IN --no-legs > $O/ab_c${n}_$rep.json 2>> $O/ab.err
+        env $ev timeout -k 10 300 python -u bench.py --full --inputs $IN --no-legs > $O/ab_c${n}_$rep.json 2>> $O/ab.err
         rc=$?
         echo "ab_c$n rc=$rc" >> $O/steps.txt
         [ $rc -ne 0 ] && exit $rc

@@ -17,7 +17,7 @@ timeout -k 10 300 python -u bench.py --write-inputs $IN > $O/write_inputs.log 2>
 for rep in 1 2; do
     for ec in "4 5" "1 5" "1 6" "4 6"; do
         set -- $ec
-        SA_LONG_CU_EVERY=$1 timeout -k 10 300 python -u bench.py --inputs $IN --no-legs --contexts $2 > $O/ab_e$1_c$2_$rep.json 2>> $O/ab.err
+        SA_LONG_CU_EVERY=$1 timeout -k 10 300 python -u bench.py --full --inputs $IN --no-legs --contexts $2 > $O/ab_e$1_c$2_$rep.json 2>> $O/ab.err
         rc=$?
         echo "ab_e$1_c$2 rc=$rc" >> $O/steps.txt
         [ $rc -ne 0 ] && exit $rc

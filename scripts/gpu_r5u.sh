@@ -21,7 +21,7 @@ SA_RB_CHUNK=2048 step lossy_tests timeout -k 10 300 python -u -m pytest tests/te
 step write_ont timeout -k 10 300 python -u bench.py --write-inputs $INO --ont --lossy 1.15 --batches 2 > $O/write_ont.log 2>&1
 for rep in 1 2; do
     for ch in 8192 4096 2048; do
-        SA_RB_CHUNK=$ch step ont_$ch timeout -k 10 300 python -u bench.py --inputs $INO --ont --lossy 1.15 --batches 2 --no-legs --steps 10 > $O/ont_${ch}_$rep.json 2>> $O/ont.err
+        SA_RB_CHUNK=$ch step ont_$ch timeout -k 10 300 python -u bench.py --full --inputs $INO --ont --lossy 1.15 --batches 2 --no-legs --steps 10 > $O/ont_${ch}_$rep.json 2>> $O/ont.err
         echo "{\"chunk\": $ch, \"rep\": $rep, \"line\": $(tail -1 $O/ont_${ch}_$rep.json)}" >> $O/ab_all.jsonl
     done
 done

@@ -45,4 +45,4 @@ for rep in 1 2; do
         && cli ingest_$rep $E/l X=1 --devices 8 --ingest-only && cli ingest_old_$rep $E/l "$OLD" --devices 8 --ingest-only || exit 1
 done
 rm -rf $E
-step bench timeout -k 10 540 python -u bench.py --e2e-log $O/e2e.log > $O/bench.json 2> $O/bench.err
+step bench timeout -k 10 540 python -u bench.py --full --e2e-log $O/e2e.log > $O/bench.json 2> $O/bench.err

@@ -23,7 +23,7 @@ step() {
 step write_inputs timeout -k 10 300 python -u bench.py --write-inputs $IN > $O/write_inputs.log 2>&1
 ab() {   # name env...
     local name=$1; shift
-    step ab_$name timeout -k 10 300 env "$@" python -u bench.py --inputs $IN --no-legs > $O/ab_$name.json 2>> $O/ab.err
+    step ab_$name timeout -k 10 300 env "$@" python -u bench.py --full --inputs $IN --no-legs > $O/ab_$name.json 2>> $O/ab.err
     echo "{\"name\": \"$name\", \"line\": $(cat $O/ab_$name.json)}" >> $O/ab_all.jsonl
 }
 ab v5 SA_RV_VARIANT=5

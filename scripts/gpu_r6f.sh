@@ -23,12 +23,12 @@ step() {
 step tests timeout -k 10 600 python -u -m pytest tests -m gpu -x -v --timeout 120 --timeout-method thread -o cache_dir=/tmp/pyc > $O/tests.log 2>&1
 step write_ont timeout -k 10 300 python -u bench.py --write-inputs $INO --ont --lossy 1.15 --batches 2 > $O/write_ont.log 2>&1
 for rep in 1 2; do
-    step ont_$rep timeout -k 10 300 python -u bench.py --inputs $INO --ont --lossy 1.15 --batches 2 --no-legs --steps 10 > $O/ont_$rep.json 2>> $O/ont.err
+    step ont_$rep timeout -k 10 300 python -u bench.py --full --inputs $INO --ont --lossy 1.15 --batches 2 --no-legs --steps 10 > $O/ont_$rep.json 2>> $O/ont.err
 done
 IN=/dev/shm/sa_bench_inputs
 step write_inputs timeout -k 10 300 python -u bench.py --write-inputs $IN > $O/write_inputs.log 2>&1
 for rep in 1 2; do
-    step ab_$rep timeout -k 10 300 python -u bench.py --inputs $IN --no-legs > $O/ab_$rep.json 2>> $O/ab.err
+    step ab_$rep timeout -k 10 300 python -u bench.py --full --inputs $IN --no-legs > $O/ab_$rep.json 2>> $O/ab.err
 done
 rm -rf $IN
-step ont_prof timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $O/ont_prof -o ont -- python3 -u bench.py --inputs $INO --ont --lossy 1.15 --batches 2 --no-legs --no-verify --steps 6 > $O/ont_prof.json 2> $O/ont_prof.err
+step ont_prof timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $O/ont_prof -o ont -- python3 -u bench.py --full --inputs $INO --ont --lossy 1.15 --batches 2 --no-legs --no-verify --steps 6 > $O/ont_prof.json 2> $O/ont_prof.err

@@ -20,10 +20,10 @@ step() {
 }
 step tests timeout -k 10 400 python -u -m pytest tests -m gpu -x -v --timeout 120 --timeout-method thread -o cache_dir=/tmp/pyc > $O/tests.log 2>&1
 step smoke timeout -k 10 200 python -u -c "import __graft_entry__ as g; g.smoke(); print('smoke ok')" > $O/smoke.log 2>&1
-step bench timeout -k 10 600 python -u bench.py --gpus 1 --steps 20 --warmup 5 --e2e-log $O/e2e_cli.log > $O/bench.json 2> $O/bench.err
+step bench timeout -k 10 600 python -u bench.py --full --gpus 1 --steps 20 --warmup 5 --e2e-log $O/e2e_cli.log > $O/bench.json 2> $O/bench.err
 step write_inputs timeout -k 10 200 python -u bench.py --write-inputs $IN > $O/write_inputs.log 2>&1
 cd /tmp
-B="$R/bench.py --inputs $IN --no-legs --no-verify --text-leg 0"
+B="$R/bench.py --full --inputs $IN --no-legs --no-verify --text-leg 0"
 step prof timeout -k 10 200 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof -o run -- python3 -u $B --steps 10 > $O/prof_bench.json 2> $O/prof_bench.err
 step solo timeout -k 10 150 rocprofv3 --kernel-trace --stats --output-format csv -d $O/solo -o run -- python3 -u $B --contexts 1 --steps 6 > $O/solo_bench.json 2> $O/solo_bench.err
 cd $R

@@ -23,7 +23,7 @@ step tests timeout -k 10 600 python -u -m pytest tests -m gpu -x -v --timeout 12
 step write_inputs timeout -k 10 300 python -u bench.py --write-inputs $IN > $O/write_inputs.log 2>&1
 for rep in 1 2; do
     for inv in 1 0; do
-        step ab_${inv}_$rep env SA_SEQ_INV=$inv timeout -k 10 300 python -u bench.py --inputs $IN --no-legs > $O/ab_${inv}_$rep.json 2>> $O/ab.err
+        step ab_${inv}_$rep env SA_SEQ_INV=$inv timeout -k 10 300 python -u bench.py --full --inputs $IN --no-legs > $O/ab_${inv}_$rep.json 2>> $O/ab.err
     done
 done
-step prof timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof -o b -- python3 -u bench.py --inputs $IN --no-legs --no-verify --steps 6 > $O/prof.json 2> $O/prof.err
+step prof timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof -o b -- python3 -u bench.py --full --inputs $IN --no-legs --no-verify --steps 6 > $O/prof.json 2> $O/prof.err

@@ -23,14 +23,14 @@ step tests timeout -k 10 600 python -u -m pytest tests -m gpu -x -v --timeout 12
 step write_ont timeout -k 10 300 python -u bench.py --write-inputs $INO --ont --lossy 1.15 --batches 2 > $O/write_ont.log 2>&1
 for rep in 1 2; do
     for ch in 7904 8192; do
-        step ont_${ch}_$rep env SA_RB_CHUNK=$ch timeout -k 10 300 python -u bench.py --inputs $INO --ont --lossy 1.15 --batches 2 --no-legs --steps 10 > $O/ont_${ch}_$rep.json 2>> $O/ont.err
+        step ont_${ch}_$rep env SA_RB_CHUNK=$ch timeout -k 10 300 python -u bench.py --full --inputs $INO --ont --lossy 1.15 --batches 2 --no-legs --steps 10 > $O/ont_${ch}_$rep.json 2>> $O/ont.err
     done
 done
 rm -rf $INO
 step write_inputs timeout -k 10 300 python -u bench.py --write-inputs $IN > $O/write_inputs.log 2>&1
 for rep in 1 2; do
     for db in 10 9; do
-        step ab_${db}_$rep env SA_BKT_DB=$db timeout -k 10 300 python -u bench.py --inputs $IN --no-legs > $O/ab_${db}_$rep.json 2>> $O/ab.err
+        step ab_${db}_$rep env SA_BKT_DB=$db timeout -k 10 300 python -u bench.py --full --inputs $IN --no-legs > $O/ab_${db}_$rep.json 2>> $O/ab.err
     done
 done
-step prof timeout -k 10 300 env SA_BKT_DB=10 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof -o b -- python3 -u bench.py --inputs $IN --no-legs --no-verify --steps 6 > $O/prof.json 2> $O/prof.err
+step prof timeout -k 10 300 env SA_BKT_DB=10 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof -o b -- python3 -u bench.py --full --inputs $IN --no-legs --no-verify --steps 6 > $O/prof.json 2> $O/prof.err

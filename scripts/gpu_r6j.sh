@@ -19,7 +19,7 @@ step() {
     if [ $rc -ne 0 ]; then exit $rc; fi
 }
 step write_ont timeout -k 10 300 python -u bench.py --write-inputs $INO --ont --lossy 1.15 --batches 2 > $O/write_ont.log 2>&1
-step ont_solo timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/ont_solo -o o -- python3 -u bench.py --inputs $INO --ont --lossy 1.15 --batches 2 --no-legs --no-verify --contexts 1 --steps 6 > $O/ont_solo.json 2> $O/ont_solo.err
+step ont_solo timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/ont_solo -o o -- python3 -u bench.py --full --inputs $INO --ont --lossy 1.15 --batches 2 --no-legs --no-verify --contexts 1 --steps 6 > $O/ont_solo.json 2> $O/ont_solo.err
 rm -rf $INO
 step write_inputs timeout -k 10 300 python -u bench.py --write-inputs $IN > $O/write_inputs.log 2>&1
-step bench_solo timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/bench_solo -o b -- python3 -u bench.py --inputs $IN --no-legs --no-verify --contexts 1 --steps 6 > $O/bench_solo.json 2> $O/bench_solo.err
+step bench_solo timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/bench_solo -o b -- python3 -u bench.py --full --inputs $IN --no-legs --no-verify --contexts 1 --steps 6 > $O/bench_solo.json 2> $O/bench_solo.err

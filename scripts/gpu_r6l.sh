@@ -28,13 +28,13 @@ INO=/dev/shm/sa_ont_inputs
 step write_ont timeout -k 10 300 python -u bench.py --write-inputs $INO --ont --lossy 1.15 --batches 2 > $O/write_ont.log 2>&1
 for rep in 1 2; do
     for pr in 64 16; do
-        step ont_${pr}_$rep env SA_PREP_ROW=$pr timeout -k 10 300 python -u bench.py --inputs $INO --ont --lossy 1.15 --batches 2 --no-legs --steps 10 > $O/ont_${pr}_$rep.json 2>> $O/ont.err
+        step ont_${pr}_$rep env SA_PREP_ROW=$pr timeout -k 10 300 python -u bench.py --full --inputs $INO --ont --lossy 1.15 --batches 2 --no-legs --steps 10 > $O/ont_${pr}_$rep.json 2>> $O/ont.err
     done
 done
 rm -rf $INO
 step write_inputs timeout -k 10 300 python -u bench.py --write-inputs $IN > $O/write_inputs.log 2>&1
-step probe_solo env SA_BKT_PROBE=$O/bkt_probe_solo.txt timeout -k 10 300 python -u bench.py --inputs $IN --no-legs --no-verify --contexts 1 --steps 4 > $O/probe_solo.json 2> $O/probe.err
-step probe_5 env SA_BKT_PROBE=$O/bkt_probe_5.txt timeout -k 10 300 python -u bench.py --inputs $IN --no-legs --no-verify --steps 10 > $O/probe_5.json 2>> $O/probe.err
+step probe_solo env SA_BKT_PROBE=$O/bkt_probe_solo.txt timeout -k 10 300 python -u bench.py --full --inputs $IN --no-legs --no-verify --contexts 1 --steps 4 > $O/probe_solo.json 2> $O/probe.err
+step probe_5 env SA_BKT_PROBE=$O/bkt_probe_5.txt timeout -k 10 300 python -u bench.py --full --inputs $IN --no-legs --no-verify --steps 10 > $O/probe_5.json 2>> $O/probe.err
 for f in solo 5; do
     python3 scripts/bkt_probe.py $O/bkt_probe_$f.txt > $O/bkt_probe_$f.summary.txt 2>&1
     head -c 4000000 $O/bkt_probe_$f.txt | gzip -c > $O/bkt_probe_$f.head.txt.gz

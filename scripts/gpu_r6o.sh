@@ -23,10 +23,10 @@ step() {
 step tests timeout -k 10 600 python -u -m pytest tests -m gpu -x -v --timeout 120 --timeout-method thread -o cache_dir=/tmp/pyc > $O/tests.log 2>&1
 step write_inputs timeout -k 10 300 python -u bench.py --write-inputs $IN > $O/write_inputs.log 2>&1
 for rep in 1 2; do
-    step ab_db9_$rep env SA_BKT_DB=9 timeout -k 10 300 python -u bench.py --inputs $IN --no-legs > $O/ab_db9_$rep.json 2>> $O/ab.err
-    step ab_db8_$rep timeout -k 10 300 python -u bench.py --inputs $IN --no-legs > $O/ab_db8_$rep.json 2>> $O/ab.err
+    step ab_db9_$rep env SA_BKT_DB=9 timeout -k 10 300 python -u bench.py --full --inputs $IN --no-legs > $O/ab_db9_$rep.json 2>> $O/ab.err
+    step ab_db8_$rep timeout -k 10 300 python -u bench.py --full --inputs $IN --no-legs > $O/ab_db8_$rep.json 2>> $O/ab.err
 done
-step probe_db9 env SA_BKT_DB=9 SA_BKT_PROBE=$O/bkt_probe_db9.txt timeout -k 10 300 python -u bench.py --inputs $IN --no-legs --no-verify --contexts 1 --steps 4 > $O/probe_db9.json 2> $O/probe.err
+step probe_db9 env SA_BKT_DB=9 SA_BKT_PROBE=$O/bkt_probe_db9.txt timeout -k 10 300 python -u bench.py --full --inputs $IN --no-legs --no-verify --contexts 1 --steps 4 > $O/probe_db9.json 2> $O/probe.err
 python3 scripts/bkt_probe.py $O/bkt_probe_db9.txt > $O/bkt_probe_db9.summary.txt 2>&1
 rm -f $O/bkt_probe_db9.txt
 mkdir -p $E/s $E/l

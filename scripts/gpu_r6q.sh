@@ -22,7 +22,7 @@ step() {
 step write_inputs timeout -k 10 300 python -u bench.py --write-inputs $IN > $O/write_inputs.log 2>&1
 for rep in 1 2; do
     for k in 2 -1 99; do
-        step ab_k${k}_$rep env SA_RV_V6_MAX=$k timeout -k 10 300 python -u bench.py --inputs $IN --no-legs > $O/ab_k${k}_$rep.json 2>> $O/ab.err
+        step ab_k${k}_$rep env SA_RV_V6_MAX=$k timeout -k 10 300 python -u bench.py --full --inputs $IN --no-legs > $O/ab_k${k}_$rep.json 2>> $O/ab.err
     done
 done
 mkdir -p $E/s $E/l

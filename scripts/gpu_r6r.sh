@@ -22,12 +22,12 @@ step() {
 }
 step tests timeout -k 10 600 python -u -m pytest tests -m gpu -x -v --timeout 120 --timeout-method thread -o cache_dir=/tmp/pyc > $O/tests.log 2>&1
 step smoke timeout -k 10 300 python -u -c "import __graft_entry__ as g; g.smoke(); print('smoke ok')" > $O/smoke.log 2>&1
-step bench timeout -k 10 900 python -u bench.py --gpus 1 --steps 20 --warmup 5 --e2e-log $O/e2e_cli.log > $O/bench.json 2> $O/bench.err
+step bench timeout -k 10 900 python -u bench.py --full --gpus 1 --steps 20 --warmup 5 --e2e-log $O/e2e_cli.log > $O/bench.json 2> $O/bench.err
 step write_inputs timeout -k 10 300 python -u bench.py --write-inputs $IN > $O/write_inputs.log 2>&1
 mkdir -p $E/l
 for k in 1 2 3; do for g in 0 1 2 3; do cat $IN/b${g}_r1.fq >> $E/l/r1.fq; cat $IN/b${g}_r2.fq >> $E/l/r2.fq; done; done
 cd /tmp
-B="$R/bench.py --inputs $IN --no-legs --no-verify --text-leg 0"
+B="$R/bench.py --full --inputs $IN --no-legs --no-verify --text-leg 0"
 step prof timeout -k 10 600 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof -o run -- python3 -u $B --steps 10 > $O/prof_bench.json 2> $O/prof_bench.err
 step solo timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/solo -o run -- python3 -u $B --contexts 1 --steps 6 > $O/solo_bench.json 2> $O/solo_bench.err
 step pmc_fetch timeout -s KILL 300 rocprofv3 --pmc FETCH_SIZE --output-format csv -d $O/pmc_fetch -o run -- python3 -u $B --steps 2 --warmup 1 > $O/pmc_fetch.json 2> $O/pmc_fetch.err

@@ -22,7 +22,7 @@ step() {
     echo "$name rc=$rc $((SECONDS - t0))s" >> $O/steps.txt
     if [ $rc -ne 0 ]; then exit $rc; fi
 }
-step ontleg timeout -k 10 600 python -u bench.py --steps 4 --warmup 2 --text-leg 0 --se-leg 0 --hash-leg 0 --e2e-batches 0 --ingest-devices 0 --cpu-seconds 0 > $O/ontleg.json 2> $O/ontleg.err
+step ontleg timeout -k 10 600 python -u bench.py --full --steps 4 --warmup 2 --text-leg 0 --se-leg 0 --hash-leg 0 --e2e-batches 0 --ingest-devices 0 --cpu-seconds 0 > $O/ontleg.json 2> $O/ontleg.err
 step write_inputs timeout -k 10 300 python -u bench.py --write-inputs $IN > $O/write_inputs.log 2>&1
 mkdir -p $E/l
 for k in 1 2 3; do for g in 0 1 2 3; do cat $IN/b${g}_r1.fq >> $E/l/r1.fq; cat $IN/b${g}_r2.fq >> $E/l/r2.fq; done; done
@@ -45,7 +45,7 @@ for rep in 1 2; do
 done
 rm -rf $E
 cd /tmp
-B="$R/bench.py --inputs $IN --no-legs --no-verify --text-leg 0"
+B="$R/bench.py --full --inputs $IN --no-legs --no-verify --text-leg 0"
 step prof5 env SA_RV_VARIANT=5 timeout -k 10 600 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof5 -o run -- python3 -u $B --steps 10 > $O/prof5_bench.json 2> $O/prof5_bench.err
 step pmc5_fetch env SA_RV_VARIANT=5 timeout -s KILL 300 rocprofv3 --pmc FETCH_SIZE --output-format csv -d $O/pmc5_fetch -o run -- python3 -u $B --steps 2 --warmup 1 > $O/pmc5_fetch.json 2> $O/pmc5_fetch.err
 step pmc5_write env SA_RV_VARIANT=5 timeout -s KILL 300 rocprofv3 --pmc WRITE_SIZE --output-format csv -d $O/pmc5_write -o run -- python3 -u $B --steps 2 --warmup 1 > $O/pmc5_write.json 2> $O/pmc5_write.err

@@ -19,11 +19,11 @@ step() {
     if [ $rc -ne 0 ]; then exit $rc; fi
 }
 cd /tmp
-step leg timeout -k 10 600 rocprofv3 --kernel-trace --stats --output-format csv -d $O/leg -o run -- python3 -u $R/bench.py --steps 2 --warmup 1 --text-leg 0 --se-leg 0 --hash-leg 0 --e2e-batches 0 --ingest-devices 0 --cpu-seconds 0 > $O/leg.json 2> $O/leg.err
+step leg timeout -k 10 600 rocprofv3 --kernel-trace --stats --output-format csv -d $O/leg -o run -- python3 -u $R/bench.py --full --steps 2 --warmup 1 --text-leg 0 --se-leg 0 --hash-leg 0 --e2e-batches 0 --ingest-devices 0 --cpu-seconds 0 > $O/leg.json 2> $O/leg.err
 cd $R
 step write_ont timeout -k 10 300 python -u bench.py --write-inputs $INO --ont --lossy 1.15 --batches 2 > $O/write_ont.log 2>&1
 cd /tmp
-step head timeout -k 10 600 rocprofv3 --kernel-trace --stats --output-format csv -d $O/head -o run -- python3 -u $R/bench.py --inputs $INO --ont --lossy 1.15 --batches 2 --no-legs --steps 10 > $O/head.json 2> $O/head.err
+step head timeout -k 10 600 rocprofv3 --kernel-trace --stats --output-format csv -d $O/head -o run -- python3 -u $R/bench.py --full --inputs $INO --ont --lossy 1.15 --batches 2 --no-legs --steps 10 > $O/head.json 2> $O/head.err
 cd $R
 python3 - $O > $O/compare.txt 2>&1 <<'PY'
 import csv, glob, statistics, sys, collections

@@ -20,6 +20,6 @@ step() {
 step write1 timeout -k 10 300 python -u bench.py --write-inputs /dev/shm/sa_ont1 --ont --lossy 1.15 --batches 1 > $O/write1.log 2>&1
 step write2 timeout -k 10 300 python -u bench.py --write-inputs /dev/shm/sa_ont2 --ont --lossy 1.15 --batches 2 > $O/write2.log 2>&1
 for rep in 1 2; do
-    step one_$rep timeout -k 10 300 python -u bench.py --inputs /dev/shm/sa_ont1 --ont --lossy 1.15 --batches 1 --no-legs --steps 10 > $O/one_$rep.json 2>> $O/ont.err
-    step two_$rep timeout -k 10 300 python -u bench.py --inputs /dev/shm/sa_ont2 --ont --lossy 1.15 --batches 2 --no-legs --steps 10 > $O/two_$rep.json 2>> $O/ont.err
+    step one_$rep timeout -k 10 300 python -u bench.py --full --inputs /dev/shm/sa_ont1 --ont --lossy 1.15 --batches 1 --no-legs --steps 10 > $O/one_$rep.json 2>> $O/ont.err
+    step two_$rep timeout -k 10 300 python -u bench.py --full --inputs /dev/shm/sa_ont2 --ont --lossy 1.15 --batches 2 --no-legs --steps 10 > $O/two_$rep.json 2>> $O/ont.err
 done

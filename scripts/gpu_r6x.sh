@@ -19,6 +19,6 @@ step() {
 }
 L="--steps 2 --warmup 1 --text-leg 0 --se-leg 0 --hash-leg 0 --e2e-batches 0 --ingest-devices 0 --cpu-seconds 0"
 for rep in 1 2; do
-    step q24_$rep timeout -k 10 600 python -u bench.py $L > $O/q24_$rep.json 2>> $O/err.log
-    step q32_$rep env SA_BENCH_HWQ=32 timeout -k 10 600 python -u bench.py $L > $O/q32_$rep.json 2>> $O/err.log
+    step q24_$rep timeout -k 10 600 python -u bench.py --full $L > $O/q24_$rep.json 2>> $O/err.log
+    step q32_$rep env SA_BENCH_HWQ=32 timeout -k 10 600 python -u bench.py --full $L > $O/q32_$rep.json 2>> $O/err.log
 done

@@ -17,6 +17,6 @@ step() {
     if [ $rc -ne 0 ]; then exit $rc; fi
 }
 L="--steps 2 --warmup 1 --text-leg 0 --e2e-batches 0 --ingest-devices 0 --cpu-seconds 0"
-step ont_1 timeout -k 10 600 python -u bench.py $L --se-leg 0 --hash-leg 0 > $O/ont_1.json 2>> $O/err.log
-step ont_2 timeout -k 10 600 python -u bench.py $L --se-leg 0 --hash-leg 0 > $O/ont_2.json 2>> $O/err.log
-step all_legs timeout -k 10 900 python -u bench.py $L > $O/all_legs.json 2>> $O/err.log
+step ont_1 timeout -k 10 600 python -u bench.py --full $L --se-leg 0 --hash-leg 0 > $O/ont_1.json 2>> $O/err.log
+step ont_2 timeout -k 10 600 python -u bench.py --full $L --se-leg 0 --hash-leg 0 > $O/ont_2.json 2>> $O/err.log
+step all_legs timeout -k 10 900 python -u bench.py --full $L > $O/all_legs.json 2>> $O/err.log

@@ -18,8 +18,8 @@ step() {
     if [ $rc -ne 0 ]; then exit $rc; fi
 }
 step write_inputs timeout -k 10 300 python -u bench.py --write-inputs $IN > $O/write_inputs.log 2>&1
-step solo env SA_RV_PROBE=$O/solo_probe.txt timeout -k 10 300 python -u bench.py --inputs $IN --no-legs --no-verify --text-leg 0 --contexts 1 --steps 6 > $O/solo.json 2> $O/solo.err
-step loaded env SA_RV_PROBE=$O/loaded_probe.txt timeout -k 10 300 python -u bench.py --inputs $IN --no-legs --no-verify --text-leg 0 --steps 10 > $O/loaded.json 2> $O/loaded.err
+step solo env SA_RV_PROBE=$O/solo_probe.txt timeout -k 10 300 python -u bench.py --full --inputs $IN --no-legs --no-verify --text-leg 0 --contexts 1 --steps 6 > $O/solo.json 2> $O/solo.err
+step loaded env SA_RV_PROBE=$O/loaded_probe.txt timeout -k 10 300 python -u bench.py --full --inputs $IN --no-legs --no-verify --text-leg 0 --steps 10 > $O/loaded.json 2> $O/loaded.err
 python3 scripts/rv_probe.py $O/solo_probe.txt $O/loaded_probe.txt > $O/report.txt 2>&1
 gzip -f $O/solo_probe.txt $O/loaded_probe.txt
 true

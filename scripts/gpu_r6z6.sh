@@ -21,13 +21,13 @@ step() {
 }
 step tests timeout -k 10 400 python -u -m pytest tests/test_gpu_parity.py -m gpu -x -v --timeout 120 --timeout-method thread -o cache_dir=/tmp/pyc -k "pass_r or coder or full_size_block or reference_test_pair or golden or many_blocks or concurrent" > $O/tests.log 2>&1
 step write_inputs timeout -k 10 300 python -u bench.py --write-inputs $IN > $O/write_inputs.log 2>&1
-B="bench.py --inputs $IN --no-legs --no-verify --text-leg 0 --steps 12"
+B="bench.py --full --inputs $IN --no-legs --no-verify --text-leg 0 --steps 12"
 for rep in 1 2; do
     step new_$rep timeout -k 10 300 python -u $B > $O/new_$rep.json 2>> $O/ab.err
     step old_$rep env SA_LIB=$R/ablib/libseqarc_amd_r6fin.so timeout -k 10 300 python -u $B > $O/old_$rep.json 2>> $O/ab.err
 done
-step solo_new env SA_RV_PROBE=$O/solo_new_probe.txt timeout -k 10 300 python -u bench.py --inputs $IN --no-legs --no-verify --text-leg 0 --contexts 1 --steps 6 > $O/solo_new.json 2> $O/solo_new.err
-step solo_old env SA_LIB=$R/ablib/libseqarc_amd_r6fin.so SA_RV_PROBE=$O/solo_old_probe.txt timeout -k 10 300 python -u bench.py --inputs $IN --no-legs --no-verify --text-leg 0 --contexts 1 --steps 6 > $O/solo_old.json 2> $O/solo_old.err
+step solo_new env SA_RV_PROBE=$O/solo_new_probe.txt timeout -k 10 300 python -u bench.py --full --inputs $IN --no-legs --no-verify --text-leg 0 --contexts 1 --steps 6 > $O/solo_new.json 2> $O/solo_new.err
+step solo_old env SA_LIB=$R/ablib/libseqarc_amd_r6fin.so SA_RV_PROBE=$O/solo_old_probe.txt timeout -k 10 300 python -u bench.py --full --inputs $IN --no-legs --no-verify --text-leg 0 --contexts 1 --steps 6 > $O/solo_old.json 2> $O/solo_old.err
 python3 scripts/rv_probe.py $O/solo_new_probe.txt $O/solo_old_probe.txt > $O/report.txt 2>&1
 gzip -f $O/solo_new_probe.txt $O/solo_old_probe.txt
 true

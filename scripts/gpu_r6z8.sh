@@ -20,7 +20,7 @@ step() {
 }
 step tests timeout -k 10 300 python -u -m pytest tests/test_gpu_parity.py -m gpu -x -v --timeout 120 --timeout-method thread -o cache_dir=/tmp/pyc -k "rblock or ont" > $O/tests.log 2>&1
 step write_ont timeout -k 10 300 python -u bench.py --write-inputs $INO --ont --lossy 1.15 --batches 2 > $O/write_ont.log 2>&1
-B="bench.py --inputs $INO --ont --lossy 1.15 --batches 2 --no-legs --steps 10"
+B="bench.py --full --inputs $INO --ont --lossy 1.15 --batches 2 --no-legs --steps 10"
 for rep in 1 2; do
     for n in 0 2 4; do
         step wg${n}_$rep env SA_RB_SPEC_WG=$n timeout -k 10 300 python -u $B > $O/wg${n}_$rep.json 2>> $O/ont.err

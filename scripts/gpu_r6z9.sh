@@ -17,4 +17,4 @@ step() {
 }
 step tests timeout -k 10 400 python -u -m pytest tests -m gpu -x -v --timeout 120 --timeout-method thread -o cache_dir=/tmp/pyc -k "rblock or ont or lossy or golden or long or prep_row or read_counter or cli" > $O/tests.log 2>&1
 step smoke timeout -k 10 200 python -u -c "import __graft_entry__ as g; g.smoke(); print('smoke ok')" > $O/smoke.log 2>&1
-step ont_leg timeout -k 10 400 python -u bench.py --steps 2 --warmup 1 --text-leg 0 --e2e-batches 0 --ingest-devices 0 --cpu-seconds 0 --se-leg 0 --hash-leg 0 > $O/ont_leg.json 2> $O/ont_leg.err
+step ont_leg timeout -k 10 400 python -u bench.py --full --steps 2 --warmup 1 --text-leg 0 --e2e-batches 0 --ingest-devices 0 --cpu-seconds 0 --se-leg 0 --hash-leg 0 > $O/ont_leg.json 2> $O/ont_leg.err

@@ -107,6 +107,14 @@ def _chunk(args):
     return out1, out2
 
 
+def chunk_jobs(n_reads: int, read_len: int = 150, paired: bool = False, seed: int = 12345,
+               genome_len: int = 5_000_000, chunk: int = 250_000, x_span: int = 0) -> list[tuple]:
+    """The arguments of _chunk for each chunk of generate()'s output, in order:
+    the chunks' (r1, r2) texts joined are generate()'s."""
+    return [(seed, ci, s, min(chunk, n_reads - s), read_len, paired, genome_len, x_span)
+            for ci, s in enumerate(range(0, n_reads, chunk))]
+
+
 def generate(n_reads: int, read_len: int = 150, paired: bool = False, seed: int = 12345,
              genome_len: int = 5_000_000, chunk: int = 250_000, progress=None, workers: int = 1,
              x_span: int = 0):
@@ -115,8 +123,7 @@ def generate(n_reads: int, read_len: int = 150, paired: bool = False, seed: int 
     x_span > 0 draws the header x coordinate from that many values (x_span = 8:
     a 50 MiB PE block's name stream is ~60 kB, near SURVEY 8's 58.7 kB; the
     default, uniform over 31000 values, gives ~195 kB)."""
-    jobs = [(seed, ci, s, min(chunk, n_reads - s), read_len, paired, genome_len, x_span)
-            for ci, s in enumerate(range(0, n_reads, chunk))]
+    jobs = chunk_jobs(n_reads, read_len, paired, seed, genome_len, chunk, x_span)
     out1: list[bytes] = []
     out2: list[bytes] = []
     if workers > 1 and len(jobs) > 1:

@@ -27,8 +27,9 @@ def test_shard_indices_cover_every_block_once():
 
 def _bench(*args):
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_PORT")}
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--dry-run", "--pairs", "2000", *args],
-                       capture_output=True, text=True, timeout=600, env=env)
+    # (--full: the end-to-end leg below is not part of a plain run)
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--dry-run", "--full", "--pairs", "2000",
+                        *args], capture_output=True, text=True, timeout=600, env=env)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
     assert len(lines) == 1, r.stdout
