@@ -78,6 +78,25 @@ class _SaRef(C.Structure):
                 ("insert_size", C.c_uint32)]
 
 
+_PATH_FIELDS = ("prep", "front_counter", "wg_per_cu", "emit", "dege_list", "seq_packed", "seq_replay", "bkt_inv",
+                "bkt_lpt", "bkt_db", "bkt_sb", "aux_sort", "aux_runs", "aux_nmod_max", "aux_dense_next", "pass_r",
+                "r_short_shared", "r_waves", "l_chunk", "l_stream", "host_waits", "long_grid", "chain_prio", "md5",
+                "rblock", "rb_spec_counter", "rb_fix_wave", "rb_apply_walk", "rb_chunk", "exact_rerun", "seq_digits",
+                "aux_digits", "front_masked")
+# the names of sa_paths' enumerated fields (include/seqarc_amd.h, SA_PATH_*)
+_PATH_NAMES = {"prep": {0: None, 1: "row16", 2: "row64", 3: "fused", 4: "wave"},
+               "emit": {0: None, 1: "row16", 2: "wave"},
+               "seq_replay": {0: None, 1: "bucket", 2: "full"},
+               "aux_sort": {0: None, 1: "dense1", 2: "dense2+copy", 3: "raw"},
+               "aux_runs": {0: None, 1: "runs_dense", 2: "find_runs"},
+               "pass_r": {0: None, 1: "rv0", 2: "rv5", 3: "rv6", 4: "lanes"},
+               "md5": {0: None, 1: "plain", 2: "pipe"}}
+
+
+class _SaPaths(C.Structure):
+    _fields_ = [(f, C.c_uint32) for f in _PATH_FIELDS]
+
+
 class _SaOut(C.Structure):
     _fields_ = [("data", C.c_void_p), ("cap", C.c_uint64), ("size", C.c_uint64)]
 
@@ -109,6 +128,7 @@ def load_library(path: str | None = None):
         "sa_parse_se": ([P, U64, P, P, P, P, P], I64), "sa_parse_pe": ([P, U64, P, U64, P, P, P, P, P], I64),
         "sa_analyze_ids": ([P, I32, P], I32),
         "sa_code_records": ([P, I32, P, P, P, P, P, U64, P], I32), "sa_coder_restarts": ([P], C.c_uint32),
+        "sa_last_paths": ([P, P], I32),
         "sa_stream_stats": ([P, P, P], None), "sa_device_bytes": ([P], U64), "sa_front_bytes": ([P], U64),
         "sa_create_shared": ([I32, P], P),
         "sa_input_create": ([I32, P, I32], P), "sa_input_destroy": ([P], None), "sa_run_input": ([P, P, P], I32),
@@ -464,6 +484,22 @@ class Encoder:
 
     def coder_restarts(self) -> int:
         return int(self._lib.sa_coder_restarts(self._ctx))
+
+    def paths(self) -> dict:
+        """What the host chose for the last run / code_records (sa_last_paths):
+        the fields of sa_paths, the enumerated ones by name (prep: row16 / row64
+        / fused / wave; emit: row16 / wave; seq_replay: bucket / full; aux_sort:
+        dense1 / dense2+copy / raw; aux_runs: runs_dense / find_runs; pass_r:
+        rv0 / rv5 / rv6 / lanes; md5: plain / pipe; None: the stage did not
+        run), the others as integers (seq_digits / aux_digits: a sort's digit
+        widths, four bits a pass, the first pass lowest)."""
+        p = _SaPaths()
+        if self._lib.sa_last_paths(self._ctx, C.byref(p)) != 0:
+            self._err("sa_last_paths")
+        out = {f: int(getattr(p, f)) for f in _PATH_FIELDS}
+        for f, names in _PATH_NAMES.items():
+            out[f] = names[out[f]]
+        return out
 
     def stream_stats(self) -> tuple[int, int]:
         """(symbols of the longest coder stream, symbols of all streams) of the last run."""

@@ -224,7 +224,7 @@ struct sa_ctx {
     void* prs_zero_p = nullptr;
     bool prs_zero_pending = false;
     uint32_t long_lds = 0;
-    bool serial_seq = false;
+    bool front_masked = false;   // (SA_RV_CUS: the front's stream on the CUs pass R leaves)
     uint32_t chain_prio = 1;   // s_setprio 3 in the latency-bound chain kernels (SA_CHAIN_PRIO=0: off)
     uint32_t md5_prio = 1;     // ... and in k_md5 (SA_MD5_PRIO; off the critical path)
     bool prep_fused = std::getenv("SA_PREP_FUSED") != nullptr;   // name columns in k_prep_sq16 (A/B)
@@ -417,6 +417,10 @@ struct sa_ctx {
     // last run
     std::vector<uint64_t> final_base, final_len;
     bool have_output = false;
+    // what the host chose for the last run (sa_last_paths): filled where the
+    // launches are chosen; paths_r: pass R's first launch of the run is in it
+    sa_paths paths{};
+    bool paths_r = false;
 
     std::vector<DBuf*> work_buffers()
     {
@@ -579,6 +583,14 @@ std::vector<int> sort_digits(int lo, int hi, int max_db = SORT_MAX_DB)
     return w;
 }
 
+// the digit widths of a sort, first pass in the low four bits (sa_paths)
+uint32_t pack_digits(const std::vector<int>& w)
+{
+    uint32_t p = 0;
+    for (size_t i = 0; i < w.size() && i < 8; i++) p |= (uint32_t)w[i] << (4 * i);
+    return p;
+}
+
 // histogram words per tile of a sort over bits [lo, hi)
 uint64_t sort_hist_per_tile(int lo, int hi, int max_db = SORT_MAX_DB)
 {
@@ -723,6 +735,11 @@ int run_rblock(sa_ctx* c, double ratio, uint64_t seq_bytes, BatchView& bv)
         SA_CHECK(c, h2d(c, c->d_rb_tab.p, c->rb_tab_host.data(), 8ull * RB_TAB_WORDS, st));
         c->rb_tab_sent = true;
     }
+    c->paths.rblock = 1;
+    c->paths.rb_spec_counter = c->rb_spec_wg > 0 ? 1u : 0u;
+    c->paths.rb_fix_wave = c->rb_fix_serial ? 0u : 1u;
+    c->paths.rb_apply_walk = c->rb_apply_walk ? 1u : 0u;
+    c->paths.rb_chunk = c->rb_chunk;
     const uint32_t* tab = c->d_rb_tab.as<uint32_t>();
     const RbChunk* dck = c->d_rb_chunks.as<RbChunk>();
     const uint32_t rgrid = (nck + RB_THREADS - 1) / RB_THREADS;
@@ -814,6 +831,13 @@ int coder_launch_r(sa_ctx* c, hipStream_t st, TaskList tl, const CoderView& cv, 
         tl.nlong = nlong;
         waves = nlong + c->rv_short_waves;
     }
+    if (!c->paths_r) {   // (the run's first pass R; the restarts' lists are short)
+        c->paths_r = true;
+        c->paths.pass_r = c->rv_lanes ? SA_PATH_R_LANES : c->rv_batch == 6 ? SA_PATH_R_V6 : c->rv_batch == 5 ? SA_PATH_R_V5 : SA_PATH_R_V0;
+        c->paths.r_short_shared = tl.nlong != tl.count ? 1u : 0u;
+        c->paths.r_waves = c->rv_lanes ? (uint32_t)RL_WAVES : c->coder_waves;
+        c->paths.chain_prio = c->chain_prio;
+    }
     if (ph >= 0) ev_begin(c, ph, st);
     tl.wait_ticks = c->rv_wait_ticks;
     if (c->rv_lanes) {   // a chain per lane, 64 per workgroup, longest first
@@ -900,6 +924,9 @@ int coder_run(sa_ctx* c, std::vector<CoderTask>& tasks, CoderView& cv, hipStream
     out_len.assign(tasks.size(), 0);
     if (tasks.empty()) return 0;
     c->coder_restarts = 0;
+    c->paths_r = false;
+    c->paths.l_chunk = c->l_chunk == 16 ? 16u : 32u;
+    c->paths.l_stream = c->st5 ? 1u : 0u;
     std::vector<uint64_t> gb;
     TaskList tl;
     uint32_t nlong = 0;
@@ -1071,7 +1098,6 @@ sa_ctx* sa_create(int device)
     const int every = ev ? std::max(1, std::atoi(ev)) : 4;
     const char* el = std::getenv("SA_LONG_LDS");
     c->long_lds = el ? (uint32_t)std::atoi(el) : 0u;
-    c->serial_seq = std::getenv("SA_SERIAL_SEQ") != nullptr;
     if (const char* cp = std::getenv("SA_CHAIN_PRIO")) c->chain_prio = std::atoi(cp) != 0;
     c->md5_prio = c->chain_prio;
     if (const char* cp = std::getenv("SA_MD5_PRIO")) c->md5_prio = std::atoi(cp) != 0;
@@ -1103,6 +1129,7 @@ sa_ctx* sa_create(int device)
         c->long_grid = std::max(1u, 6u * ncu_long);
         if (const char* lg = std::getenv("SA_LONG_GRID")) c->long_grid = (uint32_t)std::max(1, std::atoi(lg));
     }
+    c->front_masked = !m_front.empty();
     if ((m_front.empty() ? hipStreamCreateWithFlags(&c->st, hipStreamNonBlocking)
                          : hipExtStreamCreateWithCUMask(&c->st, (uint32_t)m_front.size(), m_front.data())) != hipSuccess ||
         hipExtStreamCreateWithCUMask(&c->st2, (uint32_t)m_long.size(), m_long.data()) != hipSuccess ||
@@ -1420,6 +1447,8 @@ int run_input(sa_ctx* c, const sa_input* I, const sa_cfg* cfg, bool exact, const
     const ReserveScope reserve(c->reserve_blocks, I->nblocks);
     SA_CHECK(c, hipSetDevice(c->device));
     c->have_output = false;
+    c->paths = sa_paths{};
+    c->paths.aux_dense_next = c->aux_dense ? 1u : 0u;
     if (mail_reset(c)) return -1;
     c->blocks = I->blocks;
     const uint32_t nbk = I->nblocks;
@@ -1446,14 +1475,13 @@ int run_input(sa_ctx* c, const sa_input* I, const sa_cfg* cfg, bool exact, const
     // contexts of <= 22 bits (Slevel <= 4): one sort pass over the context's low
     // 8 (9) bits, the high bkt_sb bits replayed per bucket with the models in LDS
     // (k_replay_seq_bkt); longer contexts: the full sort and k_replay_seq
-    const bool seq_bkt = c->seq_bucket && seq_sh == 2 && seq_bits >= 12 && seq_bits <= 22;
+    const bool seq_bkt = c->seq_bucket && seq_sh == 2 && bkt_applies(seq_bits);
     // (SA_BKT_DB: one more digit bit halves the models a replay wave holds in
     // LDS -- 2^12 contexts in 20 KB instead of 2^13 in 40 KB at 22 bits --
-    // for twice the waves per CU; 10 bits with the inverse-permutation pass only)
-    const int bkt_db = c->bkt_db_env >= 8 && c->bkt_db_env <= (c->seq_inv ? 10 : 9) && seq_bits - c->bkt_db_env >= 4
-                           ? c->bkt_db_env
-                           : (seq_bits <= 20 ? 8 : 9);
-    const int bkt_sb = seq_bits - bkt_db;
+    // for twice the waves per CU; 10 bits with the inverse-permutation pass only;
+    // plan_bkt refuses a width whose models do not fit the launch's LDS)
+    const BktPlan bkt = plan_bkt(seq_bits, c->bkt_db_env, c->seq_inv);
+    const int bkt_db = bkt.db, bkt_sb = bkt.sb;
     const int seq_max_db = seq_bkt ? std::max(bkt_db, (int)SORT_MAX_DB) : (int)SORT_MAX_DB;
     // (the bucket pass sorts by the context's LOW bits: k_replay_seq_bkt)
     const int seq_lo = (int)seq_sh,
@@ -1517,7 +1545,10 @@ int run_input(sa_ctx* c, const sa_input* I, const sa_cfg* cfg, bool exact, const
     SA_CHECK(c, c->d_name_p.ensure((size_t)std::max<uint32_t>(nr, 1) * 2));
     SA_CHECK(c, c->d_name_s.ensure((size_t)std::max<uint32_t>(nr, 1) * 2));
     SA_CHECK(c, c->d_maxlen.ensure((size_t)std::max<uint32_t>(nr, 1) * 2));
-    SA_CHECK(c, c->d_err.ensure(64));   // error words 0-3, the front kernels' read counters (WaveReads) 8-9
+    // error words 0-3; the counters work is taken from: 8 wq_prep, 9 wq_emit (the
+    // front kernels' reads, WaveReads), 10 wq_dege (k_emit_sq's listed reads),
+    // 11 wq_spec (k_rb_spec's chunks)
+    SA_CHECK(c, c->d_err.ensure(64));
     SA_CHECK(c, hipMemsetAsync(c->d_err.p, 0, 64, st));
 
     uint32_t* d_err = c->d_err.as<uint32_t>();
@@ -1548,6 +1579,7 @@ int run_input(sa_ctx* c, const sa_input* I, const sa_cfg* cfg, bool exact, const
         hipLaunchKernelGGL(c->md5_pipe ? k_md5<true> : k_md5<false>, dim3((uint32_t)md5t.size()), dim3(128), 0, c->st2,
                            c->d_md5tasks.as<Md5Task>(),
                            (uint32_t)md5t.size(), c->d_digests.as<uint32_t>(), c->md5_prio);
+        c->paths.md5 = c->md5_pipe ? 2u : 1u;
         ev_finish(c, PH_MD5, c->st2);
         SA_CHECK(c, hipGetLastError());
         SA_CHECK(c, hipEventRecord(c->ev_md5_done, c->st2));
@@ -1564,7 +1596,10 @@ int run_input(sa_ctx* c, const sa_input* I, const sa_cfg* cfg, bool exact, const
     // batch's prep+scan measured the same as with 16-lane rows under load, r6l:
     // 44.2 / 46.4 against 44.9 / 41.4 ms, so 16 stays the default)
     const bool prep_wide = c->prep_row == 64;
+    c->paths.wg_per_cu = c->wg_per_cu;
     if (nr) {
+        c->paths.prep = c->prep_fused ? SA_PATH_PREP_FUSED : c->prep_wave ? SA_PATH_PREP_WAVE : prep_wide ? SA_PATH_PREP_ROW64 : SA_PATH_PREP_ROW16;
+        c->paths.front_counter = wq_prep && !c->prep_wave ? 1u : 0u;   // (k_prep_sq: a static stride)
         // k_prep (names, lengths: lane per read) and k_prep_sq16 (SEQ / QUAL /
         // N-IUPAC columns: a row per read).  SA_PREP_FUSED=1: k_prep_sq16 takes
         // the name columns too (row-parallel prefix / suffix) -- measured no
@@ -1723,6 +1758,7 @@ int run_input(sa_ctx* c, const sa_input* I, const sa_cfg* cfg, bool exact, const
                            c->d_totals.as<uint32_t>(), c->d_name_p.as<int16_t>(), c->d_name_s.as<int16_t>(),
                            c->d_maxlen.as<uint16_t>(), F->d_seq_k[0].as<uint32_t>(), F->d_seq_v[0].as<uint32_t>(),
                            akb[0]->as<uint32_t>(), nullptr, d_err, dege_maxq);   // (AUX values: the index, run_sort)
+        c->paths.emit = c->emit_wave ? SA_PATH_EMIT_WAVE : SA_PATH_EMIT_ROW16;
         if (c->emit_wave) {   // (SA_EMIT_WAVE=1: round 2's wave-per-read SEQ / QUAL, for A/B)
             hipLaunchKernelGGL(k_emit_sq, dim3(wave_grid(c, nr)), dim3(64 * EMIT_WAVES), 0, st, bv,
                                c->d_counts.as<uint32_t>(), F->d_seq_k[0].as<uint32_t>(), F->d_seq_v[0].as<uint32_t>(),
@@ -1734,7 +1770,9 @@ int run_input(sa_ctx* c, const sa_input* I, const sa_cfg* cfg, bool exact, const
                                dim3(wave_grid(c, (nr + 3) / 4)), dim3(256), 0,
                                st, bv, c->d_counts.as<uint32_t>(), F->d_seq_k[0].as<uint32_t>(),
                                F->d_seq_v[0].as<uint32_t>(), akb[0]->as<uint32_t>(), nullptr, wq_emit, wqc);
+            if (wq_emit) c->paths.front_counter = 1;
             if (dege_maxq && n_ch) {   // the N / IUPAC side streams of the reads that have such bases
+                c->paths.dege_list = 1;
                 SA_CHECK(c, c->d_dege_list.ensure(4ull * ((uint64_t)nr + 1)));
                 SA_CHECK(c, hipMemsetAsync(c->d_dege_list.p, 0, 4, st));
                 hipLaunchKernelGGL(k_dege_list, dim3(std::max<uint32_t>(1, std::min<uint32_t>((nr + 255) / 256, c->n_cu * 4))),
@@ -1802,12 +1840,19 @@ int run_input(sa_ctx* c, const sa_input* I, const sa_cfg* cfg, bool exact, const
         return -1;
     ev_finish(c, PH_SORT_SEQ, st);
     ev_begin(c, PH_REPLAY_SEQ, st);
+    c->paths.seq_packed = seq_sh == 2 ? 1u : 0u;
+    if (ps.total) c->paths.seq_digits = pack_digits(sort_digits(seq_lo, seq_hi, seq_max_db));
     if (ps.total && seq_bkt) {
         const std::vector<int> dg = sort_digits(seq_lo, seq_hi, seq_max_db);   // (one pass: its digit width)
         if (dg.size() != 1) {
             c->err = "internal: the SEQ bucket sort is not one pass";
             return -1;
         }
+        c->paths.seq_replay = SA_PATH_SEQ_BUCKET;
+        c->paths.bkt_inv = seq_inv ? 1u : 0u;
+        c->paths.bkt_lpt = c->bkt_lpt ? 1u : 0u;
+        c->paths.bkt_db = (uint32_t)dg[0];
+        c->paths.bkt_sb = (uint32_t)bkt_sb;
         const uint32_t bgrid = nbk << dg[0];
         SA_CHECK(c, F->d_bkt_spare.ensure(256ull * bgrid));
         PRec* spare = F->d_bkt_spare.as<PRec>();
@@ -1858,6 +1903,7 @@ int run_input(sa_ctx* c, const sa_input* I, const sa_cfg* cfg, bool exact, const
             }
         }
     } else if (ps.total) {
+        c->paths.seq_replay = SA_PATH_SEQ_FULL;
         SA_CHECK(c, hipMemsetAsync(F->d_nseq_long.p, 0, 4, st));
         hipLaunchKernelGGL(k_replay_seq, dim3((uint32_t)ps.tile_seg.size()), dim3(SORT_THREADS), 0, st, svs,
                            F->d_seq_k[seq_sorted_buf].as<uint32_t>(), F->d_seq_v[seq_sorted_buf].as<uint32_t>(),
@@ -1878,6 +1924,9 @@ int run_input(sa_ctx* c, const sa_input* I, const sa_cfg* cfg, bool exact, const
         uint32_t dmax = 0;
         for (uint32_t b = 0; b < nbk; b++) dmax = std::max(dmax, c->h_aux_nmod[b]);
         const int dbits = dmax > 512 ? (int)AUX_DENSE_BITS : 9;
+        c->paths.aux_nmod_max = dmax;
+        c->paths.aux_sort = SA_PATH_AUX_DENSE1;
+        c->paths.aux_digits = pack_digits(sort_digits(0, dbits));
         runs_from_hist = dbits == 9 && !std::getenv("SA_FIND_RUNS");   // (SA_FIND_RUNS=1: k_find_runs, A/B)
         if (run_sort(c, st, pa, F->d_segs_aux, F->d_tile_aux, F->d_hist_aux, akb, avb, 0, dbits, aux_sorted_buf, true,
                      c->d_aux_tab.as<uint64_t>()))
@@ -1887,11 +1936,16 @@ int run_input(sa_ctx* c, const sa_input* I, const sa_cfg* cfg, bool exact, const
             SA_CHECK(c, hipMemcpyAsync(c->d_auxp_v.p, F->d_auxs_v.p, atot * 4, hipMemcpyDeviceToDevice, st));
             aux_sorted_buf = 1;
             c->aux_dense = false;   // (this input has too many models per block for one pass)
+            c->paths.aux_sort = SA_PATH_AUX_DENSE2_COPY;
         }
     } else if (run_sort(c, st, pa, F->d_segs_aux, F->d_tile_aux, F->d_hist_aux, akb, avb, AUX_SYM_BITS,
                         AUX_SYM_BITS + aux_bits, aux_sorted_buf, true)) {
         return -1;
+    } else if (pa.total) {
+        c->paths.aux_sort = SA_PATH_AUX_RAW;
+        c->paths.aux_digits = pack_digits(sort_digits(AUX_SYM_BITS, AUX_SYM_BITS + aux_bits));
     }
+    c->paths.aux_dense_next = c->aux_dense ? 1u : 0u;
     ev_finish(c, PH_SORT_AUX, st);
     ev_begin(c, PH_REPLAY_AUX, st);
     if (pa.total && akb[aux_sorted_buf] != &c->d_auxp_k) {
@@ -1905,6 +1959,7 @@ int run_input(sa_ctx* c, const sa_input* I, const sa_cfg* cfg, bool exact, const
                       c->d_huge_sorted.as<LongRun>()};
     SA_CHECK(c, hipMemsetAsync(ctr, 0, 16, st));
     if (pa.total) {
+        c->paths.aux_runs = runs_from_hist ? SA_PATH_RUNS_DENSE : SA_PATH_RUNS_FIND;
         if (runs_from_hist)
             hipLaunchKernelGGL(k_runs_dense<9>, dim3((nbk * 512u + 255) / 256), dim3(256), 0, st, sva, ak, rl);
         else
@@ -1922,6 +1977,9 @@ int run_input(sa_ctx* c, const sa_input* I, const sa_cfg* cfg, bool exact, const
     front_lock->freed = true;
     front_lock->unlock();
     hipStream_t st3 = c->st3, st4 = c->st4;
+    c->paths.host_waits = c->host_waits ? 1u : 0u;
+    c->paths.front_masked = c->front_masked ? 1u : 0u;
+    c->paths.long_grid = c->long_grid;
     if (c->host_waits) SA_CHECK(c, hipEventSynchronize(c->ev_fork_seq));
     else SA_CHECK(c, hipStreamWaitEvent(st4, c->ev_fork_seq, 0));
     if (pa.total && !c->test_skip_long)
@@ -2026,6 +2084,7 @@ int sa_run_input(sa_ctx* c, const sa_input* I, const sa_cfg* cfg)
     if (rc == 2) {   // a stream outgrew its exact payload cap (rare): drain, re-run with the bound
         for (hipStream_t s : {c->st, c->st2, c->st3, c->st4}) SA_CHECK(c, hipStreamSynchronize(s));
         rc = run_input(c, I, cfg, false);
+        c->paths.exact_rerun = 1;
     }
     if (rc) drain_after_error(c);
     return rc ? -1 : 0;
@@ -2107,6 +2166,10 @@ int sa_code_records(sa_ctx* c, int nstreams, const uint32_t* lens, const uint16_
         cm[i] = (uint16_t)cu;
     }
     hipStream_t st = c->st;
+    c->paths = sa_paths{};
+    c->paths.aux_dense_next = c->aux_dense ? 1u : 0u;
+    // (SA_RV_VARIANT holds here too; unset: the last batch's variant, 5 on a fresh context)
+    if (c->rv_variant == 0 || c->rv_variant == 5 || c->rv_variant == 6) c->rv_batch = c->rv_variant;
     SA_CHECK(c, c->d_prs_seq.ensure(prs.size() * sizeof(PRec)));
     SA_CHECK(c, c->d_cum_seq.ensure(cm.size() * 2));
     SA_CHECK(c, c->d_tasks.ensure(sizeof(CoderTask) * std::max<size_t>(tasks.size(), 1)));
@@ -2146,6 +2209,13 @@ int sa_code_records(sa_ctx* c, int nstreams, const uint32_t* lens, const uint16_
 }
 
 uint32_t sa_coder_restarts(const sa_ctx* c) { return c ? c->coder_restarts : 0; }
+
+int sa_last_paths(const sa_ctx* c, sa_paths* out)
+{
+    if (!c || !out) return -1;
+    *out = c->paths;
+    return 0;
+}
 
 uint64_t sa_device_bytes(const sa_ctx* c) { return c ? const_cast<sa_ctx*>(c)->held_bytes() : 0; }
 

@@ -38,6 +38,35 @@ inline SortPlan plan_sort(const std::vector<uint64_t>& counts)
     return p;
 }
 
+// The SEQ bucket replay (k_replay_seq_bkt): one sort pass over the context's
+// low `db` bits, then a wave per (block, digit) replays the bucket with the
+// models of the remaining high `sb` context bits in LDS.
+struct BktPlan {
+    int db, sb;
+};
+
+// contexts the bucket replay takes (packed keys only): 12..22 bits, Slevel <= 4
+inline bool bkt_applies(int seq_bits) { return seq_bits >= 12 && seq_bits <= 22; }
+
+// dynamic LDS of a k_replay_seq_bkt wave holding sb context bits
+inline uint32_t bkt_lds_bytes(int sb) { return 5u * ((1u << sb) + 64u); }
+
+constexpr uint32_t BKT_LDS_MAX = 65536;   // what a launch gets without raising the kernel's limit
+
+// The digit width for contexts of seq_bits bits.  db_env (SA_BKT_DB, 0: unset)
+// is taken when it is 8 / 9 (10 with the inverse-permutation pass, seq_inv),
+// leaves a wave at least 4 context bits and fits its models in BKT_LDS_MAX
+// (8 at 22 bits would need 82,240 B: refused); otherwise the default, 8 up to
+// 20 bits and 9 above.
+inline BktPlan plan_bkt(int seq_bits, int db_env, bool seq_inv)
+{
+    int db = seq_bits <= 20 ? 8 : 9;
+    if (db_env >= 8 && db_env <= (seq_inv ? 10 : 9) && seq_bits - db_env >= 4 &&
+        bkt_lds_bytes(seq_bits - db_env) <= BKT_LDS_MAX)
+        db = db_env;
+    return BktPlan{db, seq_bits - db};
+}
+
 struct BatchPlan {
     SortPlan seq, aux;
     std::vector<CoderTask> tasks;

@@ -177,6 +177,56 @@ uint32_t sa_coder_restarts(const sa_ctx *ctx);
  * (the serial range chain of the longest stream bounds the batch) */
 void sa_stream_stats(const sa_ctx *ctx, uint64_t *max_symbols, uint64_t *total_symbols);
 
+/* ---- path report ------------------------------------------------------ */
+/* Which kernels the host chose for the context's last sa_run / sa_run_input /
+ * sa_encode_blocks (its last sub-batch) / sa_code_records: filled where the
+ * launches are chosen, read-only, no device work.  The tests assert from it
+ * that an SA_* knob or a batch shape selected the path they mean to check.
+ * Fields of a stage that did not run are 0. */
+typedef struct {
+    uint32_t prep;            /* SA_PATH_PREP_*                                        */
+    uint32_t front_counter;   /* 1: front reads taken from a counter, 0: static stride */
+    uint32_t wg_per_cu;       /* workgroups per CU of the grid-stride front kernels    */
+    uint32_t emit;            /* SA_PATH_EMIT_*                                        */
+    uint32_t dege_list;       /* 1: k_dege_list + the listed k_emit_sq ran             */
+    uint32_t seq_packed;      /* 1: SEQ keys ctx << 2 | base, implicit values          */
+    uint32_t seq_replay;      /* SA_PATH_SEQ_*                                         */
+    uint32_t bkt_inv;         /* bucket: 1 inverse permutation, 0 scattered stores     */
+    uint32_t bkt_lpt;         /* bucket: 1 largest digits first, 0 digit order         */
+    uint32_t bkt_db;          /* bucket: the digit bits used                           */
+    uint32_t bkt_sb;          /* bucket: the context bits a wave holds in LDS          */
+    uint32_t aux_sort;        /* SA_PATH_AUX_*                                         */
+    uint32_t aux_runs;        /* SA_PATH_RUNS_*                                        */
+    uint32_t aux_nmod_max;    /* dense: the largest per-block model count read back    */
+    uint32_t aux_dense_next;  /* the context's dense flag after the batch              */
+    uint32_t pass_r;          /* SA_PATH_R_*                                           */
+    uint32_t r_short_shared;  /* 1: the short chains shared waves                      */
+    uint32_t r_waves;         /* pass-R waves per workgroup                            */
+    uint32_t l_chunk;         /* records per L-pass chunk: 16 or 32                    */
+    uint32_t l_stream;        /* 1: the L passes on a stream of their own              */
+    uint32_t host_waits;      /* 1: host-side waits between the context's streams      */
+    uint32_t long_grid;       /* k_replay_aux_long workgroups                          */
+    uint32_t chain_prio;      /* 1: the chain kernels raise their issue priority       */
+    uint32_t md5;             /* 0: none, 1: k_md5<false>, 2: k_md5<true>              */
+    uint32_t rblock;          /* 1: the R-Block pre-pass ran                           */
+    uint32_t rb_spec_counter; /* 1: k_rb_spec's chunks from a counter, 0: one grid     */
+    uint32_t rb_fix_wave;     /* 1: k_rb_fix_w, 0: k_rb_fix                            */
+    uint32_t rb_apply_walk;   /* 1: k_rb_apply, 0: k_rb_true + k_rb_fill               */
+    uint32_t rb_chunk;        /* the R-Block chunk length                              */
+    uint32_t exact_rerun;     /* 1: the exact-payload fallback re-ran the batch        */
+    uint32_t seq_digits;      /* the SEQ sort's digit widths, 4 bits a pass, first low */
+    uint32_t aux_digits;      /* the AUX sort's, likewise                              */
+    uint32_t front_masked;    /* 1: the front's stream CU-masked (SA_RV_CUS)           */
+} sa_paths;
+enum { SA_PATH_PREP_ROW16 = 1, SA_PATH_PREP_ROW64 = 2, SA_PATH_PREP_FUSED = 3, SA_PATH_PREP_WAVE = 4 };
+enum { SA_PATH_EMIT_ROW16 = 1, SA_PATH_EMIT_WAVE = 2 };
+enum { SA_PATH_SEQ_BUCKET = 1, SA_PATH_SEQ_FULL = 2 };
+enum { SA_PATH_AUX_DENSE1 = 1, SA_PATH_AUX_DENSE2_COPY = 2, SA_PATH_AUX_RAW = 3 };
+enum { SA_PATH_RUNS_DENSE = 1, SA_PATH_RUNS_FIND = 2 };
+enum { SA_PATH_R_V0 = 1, SA_PATH_R_V5 = 2, SA_PATH_R_V6 = 3, SA_PATH_R_LANES = 4 };
+/* copies the report into *out; -1 without a context or out */
+int sa_last_paths(const sa_ctx *ctx, sa_paths *out);
+
 /* ---- host-side mirrors of the reference's block plumbing -------------- */
 /* Block cut: SeqArcRead::doReadJob@0x432a80 / cultbuf@0x432530 / getEndPos@0x4320c0
  * (SE) and doReadPEJob@0x432d10 / cultPEbuf@0x432180 (PE).  Returns #blocks. */

@@ -7,7 +7,12 @@
 // extract -> sort -> replay -> code decomposition before it runs on MI355X;
 // the GPU parity tests (tests/test_gpu_parity.py) check the kernels themselves.
 //
-//   emu [-b block_bytes] [-s slevel] [-q qlevel] [-r ref.fa [-I insert]] in1.fq [in2.fq]
+//   emu [-b block_bytes] [-s slevel] [-q qlevel] [-M] [-r ref.fa [-I insert]] in1.fq [in2.fq]
+//   emu --coder | --bkt-plan
+//
+// -M: prints each block's number of distinct AUX models (what k_aux_dense
+// counts on the device: the dense AUX sort takes one pass up to 512) and stops.
+// --bkt-plan: prints plan_bkt (sa_plan.h) for every Slevel x SA_BKT_DB x SA_SEQ_INV.
 //
 // -r: the reference (HASH index) path: the oracle's index and aligner give
 // every read's alignment under both carried align_info states (what the GPU
@@ -126,6 +131,23 @@ static int coder_selftest()
     return fails || !restarts ? 1 : 0;
 }
 
+// The SEQ bucket replay's digit width (plan_bkt) over every Slevel, SA_BKT_DB
+// value and SA_SEQ_INV: one line each, checked by tests/test_plan.py.
+static int bkt_plan_table()
+{
+    static const int envs[] = {0, 7, 8, 9, 10, 11};
+    for (int slevel = 0; slevel <= 9; slevel++)
+        for (const int env : envs)
+            for (int inv = 0; inv <= 1; inv++) {
+                const int seq_bits = (2 * (slevel + 7)) & 31;
+                const BktPlan p = plan_bkt(seq_bits, env, inv != 0);
+                const bool on = bkt_applies(seq_bits);
+                std::printf("slevel %d bits %d env %d inv %d applies %d db %d sb %d lds %u\n", slevel, seq_bits, env, inv,
+                            on ? 1 : 0, p.db, p.sb, on ? bkt_lds_bytes(p.sb) : 0u);
+            }
+    return 0;
+}
+
 struct HostBlock {
     std::vector<uint8_t> names, seq, qual;
     std::vector<uint16_t> nl;
@@ -142,11 +164,13 @@ int main(int argc, char** argv)
     uint32_t insert_size = 0;
     int maxmis = 7;
     const int good = 1;
+    bool count_models = false;
     std::vector<const char*> in;
     for (int i = 1; i < argc; i++) {
         if (!std::strcmp(argv[i], "-r") && i + 1 < argc) { ref = argv[++i]; continue; }
         if (!std::strcmp(argv[i], "-I") && i + 1 < argc) { insert_size = (uint32_t)std::atoi(argv[++i]); continue; }
         if (!std::strcmp(argv[i], "-m") && i + 1 < argc) { maxmis = std::atoi(argv[++i]); continue; }
+        if (!std::strcmp(argv[i], "-M")) { count_models = true; continue; }
         if (!std::strcmp(argv[i], "-b") && i + 1 < argc) bs = std::strtoull(argv[++i], nullptr, 10);
         else if (!std::strcmp(argv[i], "-s") && i + 1 < argc) slevel = std::atoi(argv[++i]);
         else if (!std::strcmp(argv[i], "-q") && i + 1 < argc) qlevel = std::atoi(argv[++i]);
@@ -154,6 +178,7 @@ int main(int argc, char** argv)
         else in.push_back(argv[i]);
     }
     if (in.size() == 1 && !std::strcmp(in[0], "--coder")) return coder_selftest();
+    if (in.size() == 1 && !std::strcmp(in[0], "--bkt-plan")) return bkt_plan_table();
     if (in.empty()) return 2;
     std::vector<uint8_t> t1 = slurp(in[0]), t2 = in.size() > 1 ? slurp(in[1]) : std::vector<uint8_t>();
     const bool pe = in.size() > 1;
@@ -462,6 +487,16 @@ int main(int argc, char** argv)
     sort_space(sk, sv, bp.seq, 0);
     sort_space(ak, av_, bp.aux, AUX_SYM_BITS);
 
+    if (count_models) {   // -M: the distinct models of each block's AUX space (sorted by model)
+        for (size_t b = 0; b < bp.aux.segs.size(); b++) {
+            const SortSeg& g = bp.aux.segs[b];
+            uint32_t n = 0;
+            for (size_t i = g.base; i < g.base + g.count; i++)
+                n += i == g.base || (ak[i - 1] >> AUX_SYM_BITS) != (ak[i] >> AUX_SYM_BITS) ? 1u : 0u;
+            std::printf("models block %zu: %u\n", b, n);
+        }
+        return 0;
+    }
     // EMU_RUNS=1: the longest model runs per space (what bounds the replay kernels)
     if (std::getenv("EMU_RUNS")) {
         auto runs = [](const std::vector<uint32_t>& K, const SortPlan& p, int lo, const char* name) {

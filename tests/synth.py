@@ -333,3 +333,133 @@ def pe_reads_fast(g: np.ndarray, pairs: int, seed: int, L: int = 150, first: int
     s2[far] = rng.integers(0, glen - L, int(far.sum()))
     return (fixed_fastq(draw_reads(rng, g, s1, rv, L), 1, first, seed),
             fixed_fastq(draw_reads(rng, g, s2, ~rv, L), 2, first, seed))
+
+
+# ---- inputs of the GPU parity and path tests (tests/test_gpu_parity.py, tests/test_gpu_paths.py) ----
+
+def low_complexity_fastq(seed, n):
+    """Poly-A / dinucleotide / triplet repeats: BASE_MODEL context runs far longer
+    than the first halving (in-run index 242) and runs that cross sort tiles."""
+    rng = np.random.default_rng(seed)
+    recs = []
+    motifs = [b"A", b"AC", b"CAG", b"GATTACA", b"TTTTTTTTTG"]
+    for i in range(n):
+        m = motifs[i % len(motifs)]
+        s = (m * 200)[: 100 + (i % 51)]
+        if i % 7 == 0:
+            arr = bytearray(s)
+            for p in rng.integers(0, len(arr), 3):
+                arr[int(p)] = b"ACGTN"[int(rng.integers(0, 5))]
+            s = bytes(arr)
+        q = bytes(rng.choice(np.frombuffer(b"F:,#", np.uint8), size=len(s), p=[0.7, 0.2, 0.08, 0.02]))
+        # (a common name prefix of more than five bytes: the block cut's record test)
+        recs.append(b"@LOWCPLX%d\n%s\n+\n%s\n" % (i, s, q))
+    return b"".join(recs)
+
+
+def long_read_fastq(seed, n):
+    """Reads whose lengths straddle the 64-position steps of k_emit_sq, with N /
+    IUPAC bases anywhere (so a step compacts its ACGT bases) and '#' runs that
+    end the read across step boundaries (qual_nonhash) or fill it."""
+    rng = np.random.default_rng(seed)
+    lens = [0, 1, 2, 16, 17, 63, 64, 65, 127, 128, 129, 150, 191, 192, 200, 300, 1000]
+    recs = []
+    for i in range(n):
+        L = lens[i % len(lens)]
+        s = bytearray(rng.choice(np.frombuffer(b"ACGT", np.uint8), size=L))
+        rate = (0.0, 0.01, 0.2)[i % 3]
+        for p in np.nonzero(rng.random(L) < rate)[0]:
+            s[int(p)] = b"NNRYKMSWacgtn"[int(rng.integers(0, 13))]
+        q = bytearray(rng.integers(35, 75, size=L, dtype=np.uint8))
+        if L and i % 4 == 0:
+            tail = int(rng.integers(0, L + 1))
+            q[L - tail:] = b"#" * tail
+        if L and i % 5 == 1:
+            for p in np.nonzero(rng.random(L) < 0.1)[0]:
+                q[int(p)] = ord("#")
+        recs.append(b"@lr%d\n%s\n+\n%s\n" % (i, bytes(s), bytes(q)))
+    return b"".join(recs)
+
+
+def rblock_runs_fastq(seed, n, read_len):
+    """Long reads whose qualities alternate long near-constant stretches (runs
+    of rblock that cross many R-Block chunks: their speculative exits differ
+    from the true ones, so the entry pass takes rb_carry) with noisy ones
+    (chunks that converge), at random lengths, so the failing chunks fall at
+    every position of the 64-chunk windows of k_rb_fix_w."""
+    rng = np.random.default_rng(seed)
+    recs = []
+    for i in range(n):
+        q = bytearray()
+        while len(q) < read_len:
+            # (qualities below '@': a quality line never looks like a header to the cut)
+            if rng.random() < 0.5:
+                v = int(rng.integers(40, 62))
+                m = int(rng.integers(500, 40000))
+                q += bytes(np.where(rng.random(m) < 0.5, v, v + 1).astype(np.uint8))
+            else:
+                q += bytes(rng.integers(35, 64, size=int(rng.integers(50, 6000)), dtype=np.uint8))
+        q = bytes(q[:read_len])
+        s = bytes(rng.choice(np.frombuffer(b"ACGT", np.uint8), size=read_len))
+        recs.append(b"@SIMRDrb%d\n%s\n+\n%s\n" % (i, s, q))   # (the cut matches > 5 bytes of the first header)
+    return b"".join(recs)
+
+
+# model_boundary_fastq(n) with these n has exactly 512 / 513 distinct AUX models
+# in its one block at Qlevel 2 (counted by tests/cpu_emu -M, pinned by
+# tests/test_plan.py): the two sides of the dense AUX sort's one-pass limit
+MODELS_512_READS, MODELS_513_READS = 507, 508
+
+
+def model_boundary_fastq(n):
+    """n short reads, one name, whose quality strings add the quality-context
+    models one at a time: 28 reads of two qualities (a, '5'), whose second
+    symbol is coded in the context after a alone, then reads of three (a, b,
+    '5') over the pairs of the same 28 values, whose third symbol is coded in
+    the context after (a, b) -- at most one new model a read, every other
+    stream's models the same from the third read on."""
+    vals = list(range(36, 64))   # '$' .. '?': no '#' (trimmed tails), no '@'
+    quals = [bytes([a, 53]) for a in vals] + [bytes([a, b, 53]) for a in vals for b in vals]
+    assert 0 < n <= len(quals)
+    return b"".join(b"@BOUNDARY\n%s\n+\n%s\n" % (b"ACGTACGT"[:len(q)], q) for q in quals[:n])
+
+
+def prefix_suffix_names_fastq(n=3000, seed=7):
+    """Consecutive names sharing prefixes and suffixes of 0..250 bytes, names that
+    are prefixes or suffixes of their neighbour, equal names, 1-byte names, on
+    short random reads (the name columns of the prep kernels; tokenizer mode)."""
+    rng = np.random.default_rng(seed)
+    alpha = np.frombuffer(b"ABCDEFGHIJKLMNOPQRSTUVWXYZ0123456789:_-./", dtype=np.uint8)
+
+    def word(n):
+        return bytes(alpha[rng.integers(0, len(alpha), n)])
+
+    names, prev = [], word(40)
+    for i in range(n):
+        kind = i % 6
+        if kind == 0:
+            p, s, m = int(rng.integers(0, 120)), int(rng.integers(0, 120)), int(rng.integers(0, 16))
+            nm = prev[:p] + word(m) + prev[len(prev) - min(s, len(prev)):]
+        elif kind == 1:
+            nm = prev
+        elif kind == 2:
+            nm = prev[:int(rng.integers(1, len(prev) + 1))]
+        elif kind == 3:
+            nm = prev[int(rng.integers(0, len(prev))):]
+        elif kind == 4:
+            nm = word(int(rng.integers(1, 250)))
+        else:
+            nm = word(1) if rng.integers(0, 2) else prev + word(int(rng.integers(0, 60)))
+        nm = (nm or b"X")[:245]
+        names.append(nm)
+        prev = nm
+    # every header starts with the first one's first bytes (the block cut looks for
+    # "\n@" + more than five bytes of the file's first line, end_pos)
+    names = [b"SIMRD" + nm for nm in names]
+    recs = []
+    for nm in names:
+        L = int(rng.integers(20, 120))
+        seq = bytes(np.frombuffer(b"ACGT", dtype=np.uint8)[rng.integers(0, 4, L)])
+        qual = bytes(rng.integers(35, 64, L).astype(np.uint8))   # (no '@' in the qualities)
+        recs.append(b"@" + nm + b"\n" + seq + b"\n+\n" + qual + b"\n")
+    return b"".join(recs)

@@ -14,6 +14,11 @@ import fastqueeze_amd as fq
 
 pytestmark = pytest.mark.gpu
 
+# (the generators these tests share with tests/test_gpu_paths.py live in tests/synth.py)
+_low_complexity_fastq = synth.low_complexity_fastq
+_long_read_fastq = synth.long_read_fastq
+_rblock_runs_fastq = synth.rblock_runs_fastq
+
 
 @pytest.fixture(scope="module")
 def enc():
@@ -69,41 +74,7 @@ def test_name_prefix_suffix_lengths(enc):
     """k_prep_sq16's row-parallel name columns (name_prefix_suffix): consecutive
     names sharing prefixes and suffixes of 0..250 bytes, names that are prefixes
     or suffixes of their neighbour, equal names, 1-byte names; tokenizer mode."""
-    rng = np.random.default_rng(7)
-    alpha = np.frombuffer(b"ABCDEFGHIJKLMNOPQRSTUVWXYZ0123456789:_-./", dtype=np.uint8)
-
-    def word(n):
-        return bytes(alpha[rng.integers(0, len(alpha), n)])
-
-    names, prev = [], word(40)
-    for i in range(3000):
-        kind = i % 6
-        if kind == 0:
-            p, s, m = int(rng.integers(0, 120)), int(rng.integers(0, 120)), int(rng.integers(0, 16))
-            nm = prev[:p] + word(m) + prev[len(prev) - min(s, len(prev)):]
-        elif kind == 1:
-            nm = prev
-        elif kind == 2:
-            nm = prev[:int(rng.integers(1, len(prev) + 1))]
-        elif kind == 3:
-            nm = prev[int(rng.integers(0, len(prev))):]
-        elif kind == 4:
-            nm = word(int(rng.integers(1, 250)))
-        else:
-            nm = word(1) if rng.integers(0, 2) else prev + word(int(rng.integers(0, 60)))
-        nm = (nm or b"X")[:245]
-        names.append(nm)
-        prev = nm
-    # every header starts with the first one's first bytes (the block cut looks for
-    # "\n@" + more than five bytes of the file's first line, end_pos)
-    names = [b"SIMRD" + nm for nm in names]
-    recs = []
-    for nm in names:
-        L = int(rng.integers(20, 120))
-        seq = bytes(np.frombuffer(b"ACGT", dtype=np.uint8)[rng.integers(0, 4, L)])
-        qual = bytes(rng.integers(35, 64, L).astype(np.uint8))   # (no '@' in the qualities)
-        recs.append(b"@" + nm + b"\n" + seq + b"\n+\n" + qual + b"\n")
-    blocks = fq.blocks_from_fastq(b"".join(recs), None, 100_000)
+    blocks = fq.blocks_from_fastq(synth.prefix_suffix_names_fastq(), None, 100_000)
     assert len(blocks) > 2
     _check(enc, blocks, fq.Config(bin_mode=0))
 
@@ -252,24 +223,6 @@ def test_low_complexity_context_runs(enc):
         _check(enc, blocks, fq.Config(slevel=slevel))
 
 
-def _low_complexity_fastq(seed, n):
-    rng = np.random.default_rng(seed)
-    recs = []
-    motifs = [b"A", b"AC", b"CAG", b"GATTACA", b"TTTTTTTTTG"]
-    for i in range(n):
-        m = motifs[i % len(motifs)]
-        s = (m * 200)[: 100 + (i % 51)]
-        if i % 7 == 0:
-            arr = bytearray(s)
-            for p in rng.integers(0, len(arr), 3):
-                arr[int(p)] = b"ACGTN"[int(rng.integers(0, 5))]
-            s = bytes(arr)
-        q = bytes(rng.choice(np.frombuffer(b"F:,#", np.uint8), size=len(s), p=[0.7, 0.2, 0.08, 0.02]))
-        # (a common name prefix of more than five bytes: the block cut's record test)
-        recs.append(b"@LOWCPLX%d\n%s\n+\n%s\n" % (i, s, q))
-    return b"".join(recs)
-
-
 @pytest.mark.parametrize("lanes,bucket,variant,inv,db,lpt", [(0, 0, 6, 1, 0, 1), (1, 1, 6, 1, 0, 1),
                                                              (1, 0, 6, 1, 0, 1), (0, 1, 6, 1, 0, 1),
                                                              (0, 1, 5, 1, 0, 1), (0, 1, 0, 1, 0, 1),
@@ -311,30 +264,6 @@ def test_pass_r_and_seq_replay_paths(monkeypatch, lanes, bucket, variant, inv, d
         e.close()
 
 
-def _long_read_fastq(seed, n):
-    """Reads whose lengths straddle the 64-position steps of k_emit_sq, with N /
-    IUPAC bases anywhere (so a step compacts its ACGT bases) and '#' runs that
-    end the read across step boundaries (qual_nonhash) or fill it."""
-    rng = np.random.default_rng(seed)
-    lens = [0, 1, 2, 16, 17, 63, 64, 65, 127, 128, 129, 150, 191, 192, 200, 300, 1000]
-    recs = []
-    for i in range(n):
-        L = lens[i % len(lens)]
-        s = bytearray(rng.choice(np.frombuffer(b"ACGT", np.uint8), size=L))
-        rate = (0.0, 0.01, 0.2)[i % 3]
-        for p in np.nonzero(rng.random(L) < rate)[0]:
-            s[int(p)] = b"NNRYKMSWacgtn"[int(rng.integers(0, 13))]
-        q = bytearray(rng.integers(35, 75, size=L, dtype=np.uint8))
-        if L and i % 4 == 0:
-            tail = int(rng.integers(0, L + 1))
-            q[L - tail:] = b"#" * tail
-        if L and i % 5 == 1:
-            for p in np.nonzero(rng.random(L) < 0.1)[0]:
-                q[int(p)] = ord("#")
-        recs.append(b"@lr%d\n%s\n+\n%s\n" % (i, bytes(s), bytes(q)))
-    return b"".join(recs)
-
-
 @pytest.mark.parametrize("slevel,qlevel", [(3, 2), (1, 3), (4, 1), (9, 2)])
 def test_long_reads_emit_steps(enc, slevel, qlevel):
     """SEQ contexts and QUAL contexts carried across k_emit_sq's 64-position steps."""
@@ -368,30 +297,6 @@ def test_lossy_rblock(enc, test_pair, ratio):
     t1, _ = synth.generate(60, paired=False, seed=11, read_len=20000)
     _check(enc, fq.blocks_from_fastq(t1), fq.Config(lossy=ratio))
     _check(enc, fq.blocks_from_fastq(synth.edge_cases()), fq.Config(lossy=ratio, md5=False))
-
-
-def _rblock_runs_fastq(seed, n, read_len):
-    """Long reads whose qualities alternate long near-constant stretches (runs
-    of rblock that cross many R-Block chunks: their speculative exits differ
-    from the true ones, so the entry pass takes rb_carry) with noisy ones
-    (chunks that converge), at random lengths, so the failing chunks fall at
-    every position of the 64-chunk windows of k_rb_fix_w."""
-    rng = np.random.default_rng(seed)
-    recs = []
-    for i in range(n):
-        q = bytearray()
-        while len(q) < read_len:
-            # (qualities below '@': a quality line never looks like a header to the cut)
-            if rng.random() < 0.5:
-                v = int(rng.integers(40, 62))
-                m = int(rng.integers(500, 40000))
-                q += bytes(np.where(rng.random(m) < 0.5, v, v + 1).astype(np.uint8))
-            else:
-                q += bytes(rng.integers(35, 64, size=int(rng.integers(50, 6000)), dtype=np.uint8))
-        q = bytes(q[:read_len])
-        s = bytes(rng.choice(np.frombuffer(b"ACGT", np.uint8), size=read_len))
-        recs.append(b"@SIMRDrb%d\n%s\n+\n%s\n" % (i, s, q))   # (the cut matches > 5 bytes of the first header)
-    return b"".join(recs)
 
 
 @pytest.mark.parametrize("serial,spec_wg", [("0", "2"), ("1", "2"), ("0", "0")])
