@@ -22,7 +22,7 @@ import numpy as np
 from . import build as _build
 
 __all__ = ["SeqArcError", "blocks_from_fastq", "Block", "Config", "Encoder", "cut_se", "cut_pe", "parse_se", "parse_pe", "analyze_ids",
-           "load_library", "BLOCK_SIZE", "Input"]
+           "load_library", "BLOCK_SIZE", "Input", "bgzf_scan", "Inflater", "BGZF_MEMBER", "INFLATE_STATUS"]
 
 BLOCK_SIZE = 50 << 20   # SeqArcParam BlockSize(M) = 50 (ctor @0x40776f)
 
@@ -148,6 +148,11 @@ def load_library(path: str | None = None):
         "sa_hash_load": ([P, P, U64], P), "sa_hash_packed": ([P, P, P, U64], I32),
         "sa_hash_align_kernel_ms": ([P], C.c_float),
         "sa_decode_block_ref": ([P, U64, P, P, I32, P, P], I64),
+        "sa_bgzf_scan": ([P, U64, P, U64, P, P], I64),
+        "sa_inflater_create": ([I32], P), "sa_inflater_destroy": ([P], None),
+        "sa_inflate_members": ([P, P, U64, P, C.c_uint32, P, U64, P], I32),
+        "sa_inflater_error": ([P], C.c_char_p), "sa_inflater_kernel_ms": ([P], C.c_float),
+        "sa_inflater_grid": ([P], C.c_uint32),
     }
     for name, (args, res) in sigs.items():
         fn = getattr(lib, name)
@@ -537,6 +542,94 @@ class HostBuffer:
             self.close()
         except Exception:
             pass
+
+
+# sa_bgzf_member (include/seqarc_amd.h): a member's deflate bytes in the input and its place in the output
+BGZF_MEMBER = np.dtype([("in_off", "<u8"), ("in_len", "<u4"), ("out_off", "<u8"), ("isize", "<u4"), ("crc", "<u4")],
+                       align=True)
+INFLATE_STATUS = {0: "ok", 1: "input overrun", 2: "bad block type or stored length", 3: "bad code lengths",
+                  4: "distance too far", 5: "output size is not ISIZE", 6: "CRC mismatch"}
+
+
+def bgzf_scan(data, max_members: int | None = None):
+    """sa_bgzf_scan: the whole BGZF members of `data` as a BGZF_MEMBER array, the
+    bytes they take and the bytes they inflate to.  A member cut by the end of
+    `data` is left out (consumed < len(data)); raises on anything that is not BGZF."""
+    lib = load_library()
+    a = _as_u8(data)
+    cap = max_members if max_members is not None else a.size // 26 + 1
+    ms = np.zeros(max(1, cap), BGZF_MEMBER)
+    consumed, out_bytes = C.c_uint64(0), C.c_uint64(0)
+    n = lib.sa_bgzf_scan(_ptr(a), a.size, ms.ctypes.data, cap, C.byref(consumed), C.byref(out_bytes))
+    if n < 0:
+        raise SeqArcError({-1: "not BGZF (malformed member header)", -2: "a BGZF member larger than 64 KiB",
+                           -3: f"more than {cap} BGZF members"}.get(n, f"sa_bgzf_scan: {n}"))
+    return ms[:n], consumed.value, out_bytes.value
+
+
+class Inflater:
+    """BGZF members inflated on the device (sa_inflater_*): one wave per member,
+    CRC-32 checked there.  Its device slabs grow on demand and are kept."""
+
+    def __init__(self, device: int = 0):
+        self._lib = load_library()
+        self._h = self._lib.sa_inflater_create(device)
+        if not self._h:
+            raise SeqArcError(f"sa_inflater_create failed: no usable gfx950 device {device}")
+
+    def close(self):
+        if self._h:
+            self._lib.sa_inflater_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    @property
+    def last_kernel_ms(self) -> float:
+        return float(self._lib.sa_inflater_kernel_ms(self._h))
+
+    @property
+    def grid(self) -> int:
+        """(tests and diagnostics) Workgroups (waves) a launch uses at most (SA_INFL_GRID)."""
+        return int(self._lib.sa_inflater_grid(self._h))
+
+    def inflate_into(self, data, members: np.ndarray, out: np.ndarray) -> tuple[int, np.ndarray]:
+        """sa_inflate_members into the uint8 array `out`; (return value, status)."""
+        a = _as_u8(data)
+        ms = np.ascontiguousarray(members, BGZF_MEMBER)
+        status = np.zeros(max(1, ms.size), np.uint32)
+        rc = self._lib.sa_inflate_members(self._h, _ptr(a), a.size, ms.ctypes.data, ms.size, _ptr(out), out.size,
+                                          status.ctypes.data)
+        if rc < 0:
+            raise SeqArcError(f"sa_inflate_members ({rc}): {self._lib.sa_inflater_error(self._h).decode()}")
+        return rc, status[:ms.size]
+
+    def inflate_members(self, data, members: np.ndarray) -> tuple[bytes, np.ndarray]:
+        """The members' output (a buffer that ends with the last member's bytes;
+        a failed member's range is undefined) and the per-member status."""
+        ms = np.ascontiguousarray(members, BGZF_MEMBER)
+        size = int((ms["out_off"] + ms["isize"]).max()) if ms.size else 0
+        out = np.zeros(size, np.uint8)
+        _, status = self.inflate_into(data, ms, out)
+        return out.tobytes(), status
+
+    def inflate_bgzf(self, data) -> bytes:
+        """A whole BGZF file's text."""
+        a = _as_u8(data)
+        ms, consumed, _ = bgzf_scan(a)
+        if consumed != a.size:
+            raise SeqArcError(f"BGZF input ends inside a member (at byte {consumed} of {a.size})")
+        out, status = self.inflate_members(a, ms)
+        bad = np.flatnonzero(status)
+        if bad.size:
+            i = int(bad[0])
+            raise SeqArcError(f"BGZF member {i} failed to inflate: status {int(status[i])} "
+                              f"({INFLATE_STATUS.get(int(status[i]), '?')})")
+        return out
 
 
 class Input:

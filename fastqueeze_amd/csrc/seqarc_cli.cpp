@@ -25,6 +25,8 @@
 //   --writers N      archive writer threads (default 8: page maps at the blocks' offsets; 1: write(2))
 //   --ingest-only    the reader and block cut alone, batches dealt to devices x contexts
 //                    consumers (no device); --ingest-crc: the consumers CRC the texts
+//   --gpu-inflate    BGZF inputs are inflated on the first device (sa_inflate_members)
+//                    instead of on host threads; other gzip files keep the host path
 //
 // Compression mirrors SeqArc-1.6 main@0x41fd40 -> SeqArcContext::doReadAndEncode
 // @0x41a4e0 as a stream: one reader thread cuts 50 MiB blocks as the input
@@ -77,11 +79,12 @@ int usage()
             "usage: seqarc_amd -c [-t N] [-l R] [-n] [-f] [-p] -1 A.fq[.gz] [-2 B.fq[.gz]] (-o OUT | OUT)\n"
             "                  [--slevel K] [--qlevel Q] [--devices N] [--contexts K] [--batch BLOCKS]\n"
             "                  [--block-size MiB] [--device D] [--share-device] [--ramp] [--release]\n"
-            "                  [--stage-ahead] [--writers N] [--read-threads N]\n"
+            "                  [--stage-ahead] [--writers N] [--read-threads N] [--gpu-inflate]\n"
             "       seqarc_amd -d [-t N] [-f] [-p] [-P 1|2|3] [ref.fa] ARCHIVE.arc [PREFIX] [-o PREFIX]\n"
             "       seqarc_amd -i ref.fa            (HASH index: ref.fa.hash + ref.fa.md5)\n"
             "       (-s with -i / -c / -d and ref.fa: the index image in /dev/shm/<ref file name>)\n"
-            "       (-c / -d with ref.fa: the reference path; -I N insert size, --maxmis M)\n");
+            "       (-c / -d with ref.fa: the reference path; -I N insert size, --maxmis M)\n"
+            "       (--gpu-inflate: BGZF inputs of -c are inflated on the first device, not on host threads)\n");
     return 2;
 }
 
@@ -356,6 +359,10 @@ struct GzStream {
     size_t cur_at = 0;
     static constexpr size_t kMaxQueued = 512u << 20;
 
+    int gpu_device = -1;   // >= 0 (--gpu-inflate): BGZF members are inflated on this device
+    bool verbose = false;
+    std::string name;
+
     bool start(int f, int w)
     {
         fd = f;
@@ -366,7 +373,9 @@ struct GzStream {
                h[12] == 'B' && h[13] == 'C' && h[14] == 2 && h[15] == 0;
         prod = std::thread([this]() {
             lower_priority();
-            const bool ok = bgzf ? run_bgzf() : run_plain();
+            if (gpu_device >= 0 && !bgzf && verbose)
+                fprintf(stderr, "seqarc_amd: --gpu-inflate: %s is gzip but not BGZF, inflating it on the host\n", name.c_str());
+            const bool ok = bgzf ? (gpu_device >= 0 ? run_bgzf_gpu() : run_bgzf()) : run_plain();
             std::lock_guard<std::mutex> g(mu);
             failed = !ok;
             done = true;
@@ -607,6 +616,261 @@ struct GzStream {
         }
         return finish(true);
     }
+    // BGZF with --gpu-inflate: the same slabs, carry and in-order retirement, but
+    // a slab's members are walked by sa_bgzf_scan and inflated on the device by
+    // sa_inflate_members (one sa_inflater per input, driven by one thread in
+    // place of the `workers` pool) while this thread reads and scans the next
+    // slabs, up to kInFlight ahead.  Slabs are read into recycled page-locked
+    // buffers (the H2D copy is a DMA) and inflate into one of two page-locked
+    // output slabs, from which a copier thread copies the text into the queue's
+    // chunk while the next device call fills the other slab.  Within the gpu
+    // thread H2D, kernel and D2H of a call still run one after the other.
+    bool run_bgzf_gpu()
+    {
+        const size_t kSlab = 32u << 20;
+        const size_t kInFlight = 4;
+        const uint64_t kGroupOut = 512ull << 20;   // output bytes per device call (a slab of long runs inflates 1000-fold)
+        struct Slab {
+            uint8_t* in = nullptr;   // sa_host_alloc, kSlab bytes
+            std::vector<sa_bgzf_member> ms;
+        };
+        auto now = []() { return std::chrono::steady_clock::now(); };
+        auto ms_since = [&](std::chrono::steady_clock::time_point t) {
+            return std::chrono::duration<double, std::milli>(now() - t).count();
+        };
+        const auto t_begin = now();
+        sa_inflater* infl = sa_inflater_create(gpu_device);
+        const double create_ms = ms_since(t_begin);
+        if (!infl) {
+            fprintf(stderr, "seqarc_amd: --gpu-inflate: no usable gfx950 device %d\n", gpu_device);
+            return false;
+        }
+        std::mutex pm;
+        std::condition_variable pcv;
+        std::deque<std::unique_ptr<Slab>> jobs;   // in file order
+        std::vector<uint8_t*> free_in;
+        bool quit = false, bad = false, stopped = false;
+        // -v: where the input's time went (the device calls run one after the other on the gpu
+        // thread, the host copies on the copier thread beside them)
+        double kernel_ms = 0, call_ms = 0, copy_ms = 0, push_ms = 0, alloc_ms = 0, idle_ms = 0, in_alloc_ms = 0, out_wait_ms = 0;
+        uint64_t n_slabs = 0, n_members = 0, text_bytes = 0;
+        std::thread gpu([&]() {
+            lower_priority();
+            // two output slabs: while the copier thread copies one into the queue's chunk,
+            // the next device call fills the other
+            struct Out {
+                uint8_t* p = nullptr;
+                uint64_t cap = 0, bytes = 0;
+                bool busy = false;   // handed to the copier
+            } outs[2];
+            std::mutex cm;
+            std::condition_variable ccv;
+            std::deque<int> handed;   // output slabs to copy, in order
+            bool cquit = false, cgone = false;
+            std::thread copier([&]() {
+                lower_priority();
+                for (;;) {
+                    int k;
+                    {
+                        std::unique_lock<std::mutex> lk(cm);
+                        ccv.wait(lk, [&] { return cquit || !handed.empty(); });
+                        if (handed.empty()) break;
+                        k = handed.front();
+                    }
+                    bool ok = true;
+                    if (!cgone) {   // (only this thread writes cgone)
+                        auto t0 = now();
+                        Bytes chunk(outs[k].bytes);
+                        memcpy(chunk.data(), outs[k].p, outs[k].bytes);
+                        copy_ms += ms_since(t0);
+                        t0 = now();
+                        ok = push(std::move(chunk));
+                        push_ms += ms_since(t0);   // (the queue is full: the block cut is behind)
+                    }
+                    std::lock_guard<std::mutex> g(cm);
+                    if (!ok) cgone = true;
+                    handed.pop_front();
+                    outs[k].busy = false;
+                    ccv.notify_all();
+                }
+            });
+            int turn = 0;
+            std::vector<sa_bgzf_member> grp;
+            for (;;) {
+                std::unique_ptr<Slab> s;
+                {
+                    const auto t0 = now();
+                    std::unique_lock<std::mutex> lk(pm);
+                    pcv.wait(lk, [&] { return quit || !jobs.empty(); });
+                    idle_ms += ms_since(t0);   // (waiting for the reader's next slab)
+                    if (jobs.empty()) break;
+                    s = std::move(jobs.front());   // (it leaves the queue when it is done: the reader counts it in flight)
+                }
+                bool fail = false, gone = false;
+                for (size_t a = 0; a < s->ms.size() && !fail && !gone;) {
+                    size_t b = a;
+                    uint64_t total = 0;
+                    while (b < s->ms.size() && (b == a || total + s->ms[b].isize <= kGroupOut)) total += s->ms[b++].isize;
+                    const uint64_t in0 = s->ms[a].in_off, in1 = s->ms[b - 1].in_off + s->ms[b - 1].in_len;
+                    grp.assign(s->ms.begin() + (std::ptrdiff_t)a, s->ms.begin() + (std::ptrdiff_t)b);
+                    const uint64_t out0 = grp[0].out_off;
+                    for (sa_bgzf_member& m : grp) {
+                        m.in_off -= in0;
+                        m.out_off -= out0;
+                    }
+                    Out& o = outs[turn];
+                    turn ^= 1;
+                    {
+                        const auto t0 = now();
+                        std::unique_lock<std::mutex> lk(cm);
+                        ccv.wait(lk, [&] { return !o.busy; });
+                        out_wait_ms += ms_since(t0);   // (the copier still holds this slab)
+                        if (cgone) {
+                            gone = true;
+                            break;
+                        }
+                    }
+                    if (total > o.cap) {
+                        const auto t0 = now();
+                        if (o.p) sa_host_free(o.p);
+                        o.cap = total + total / 8;
+                        o.p = static_cast<uint8_t*>(sa_host_alloc(o.cap));
+                        if (!o.p) {
+                            fprintf(stderr, "seqarc_amd: --gpu-inflate: cannot allocate %llu bytes of host memory\n",
+                                    (unsigned long long)o.cap);
+                            o.cap = 0;
+                            fail = true;
+                            break;
+                        }
+                        alloc_ms += ms_since(t0);
+                    }
+                    auto t0 = now();
+                    const int rc = sa_inflate_members(infl, s->in + in0, in1 - in0, grp.data(), (uint32_t)grp.size(), o.p, total,
+                                                      nullptr);
+                    if (rc < 0) fprintf(stderr, "seqarc_amd: --gpu-inflate: %s\n", sa_inflater_error(infl));
+                    if (rc != 0) {   // (> 0: members that do not inflate or whose CRC differs -- the host path's error)
+                        fail = true;
+                        break;
+                    }
+                    call_ms += ms_since(t0);
+                    kernel_ms += sa_inflater_kernel_ms(infl);
+                    n_members += grp.size();
+                    text_bytes += total;
+                    if (total) {
+                        std::lock_guard<std::mutex> g(cm);
+                        o.bytes = total;
+                        o.busy = true;
+                        handed.push_back((int)(&o - outs));
+                        ccv.notify_all();
+                    }
+                    a = b;
+                }
+                n_slabs++;
+                std::lock_guard<std::mutex> g(pm);
+                free_in.push_back(s->in);
+                jobs.pop_front();
+                if (fail) bad = true;
+                if (gone) stopped = true;
+                pcv.notify_all();
+                if (fail || gone) break;
+            }
+            {
+                std::lock_guard<std::mutex> g(cm);
+                cquit = true;
+            }
+            ccv.notify_all();
+            copier.join();   // (it copies what was handed to it first)
+            if (cgone) {
+                std::lock_guard<std::mutex> g(pm);
+                stopped = true;
+                pcv.notify_all();
+            }
+            for (Out& o : outs)
+                if (o.p) sa_host_free(o.p);
+        });
+        auto finish = [&](bool rc) {
+            {
+                std::lock_guard<std::mutex> g(pm);
+                quit = true;
+            }
+            pcv.notify_all();
+            gpu.join();   // (it drains the queue unless a slab failed or the reader went away)
+            {
+                std::lock_guard<std::mutex> g(pm);
+                for (auto& j : jobs) free_in.push_back(j->in);
+                jobs.clear();
+                rc = rc && !bad;
+            }
+            for (uint8_t* p : free_in) sa_host_free(p);
+            if (verbose)
+                fprintf(stderr,
+                        "seqarc_amd: --gpu-inflate: %s: %llu slab(s), %llu member(s), %llu text bytes on device %d in %.1f ms: "
+                        "inflater create %.1f ms, slab alloc %.1f + %.1f ms, sa_inflate_members %.1f ms (inflate kernel %.1f ms), "
+                        "host copy %.1f ms beside them (the device thread waited %.1f ms for it), queue wait %.1f ms, waiting for slabs "
+                        "%.1f ms\n",
+                        name.c_str(), (unsigned long long)n_slabs, (unsigned long long)n_members,
+                        (unsigned long long)text_bytes, gpu_device, ms_since(t_begin), create_ms, in_alloc_ms, alloc_ms, call_ms,
+                        kernel_ms, copy_ms, out_wait_ms, push_ms, idle_ms);
+            sa_inflater_destroy(infl);
+            return rc;
+        };
+        std::vector<uint8_t> carry_buf;   // a member cut by the end of the previous slab
+        uint64_t at = 0;
+        bool eof = false;
+        while (!eof || !carry_buf.empty()) {
+            std::unique_ptr<Slab> s(new Slab());
+            {
+                // a slab's buffer: a recycled one, a new one while fewer than kInFlight + 1 exist
+                std::unique_lock<std::mutex> lk(pm);
+                pcv.wait(lk, [&] { return bad || stopped || jobs.size() < kInFlight; });
+                if (bad) { lk.unlock(); return finish(false); }
+                if (stopped) { lk.unlock(); return finish(true); }
+                if (!free_in.empty()) {
+                    s->in = free_in.back();
+                    free_in.pop_back();
+                }
+            }
+            if (!s->in) {
+                const auto t0 = now();
+                s->in = static_cast<uint8_t*>(sa_host_alloc(kSlab));
+                in_alloc_ms += ms_since(t0);
+            }
+            if (!s->in) return finish(false);
+            auto drop = [&](bool rc) {
+                {
+                    std::lock_guard<std::mutex> g(pm);
+                    free_in.push_back(s->in);
+                }
+                return finish(rc);
+            };
+            const size_t c0 = carry_buf.size();
+            if (c0) memcpy(s->in, carry_buf.data(), c0);
+            carry_buf.clear();
+            const long r = eof ? 0 : readn(s->in + c0, kSlab - c0, at);
+            if (r < 0) return drop(false);
+            if ((size_t)r < kSlab - c0) eof = true;
+            const size_t have = c0 + (size_t)r;
+            if (eof && have == 0) return drop(true);
+            s->ms.resize(have / 26 + 1);   // (a member is at least 26 bytes: header 18, no deflate bytes, trailer 8)
+            uint64_t consumed = 0, total = 0;
+            const int64_t n = sa_bgzf_scan(s->in, have, s->ms.data(), s->ms.size(), &consumed, &total);
+            // not BGZF after all; or no whole member: a truncated member, or trailing bytes that are no member
+            if (n <= 0) return drop(false);
+            s->ms.resize((size_t)n);
+            carry_buf.assign(s->in + consumed, s->in + have);
+            if (eof && !carry_buf.empty() && carry_buf.size() < 18) return drop(false);
+            {
+                std::lock_guard<std::mutex> g(pm);
+                jobs.push_back(std::move(s));
+            }
+            pcv.notify_all();
+        }
+        {
+            std::unique_lock<std::mutex> lk(pm);
+            pcv.wait(lk, [&] { return bad || stopped || jobs.empty(); });
+        }
+        return finish(true);
+    }
     // up to n bytes into dst; 0 at the end; -1 on a gzip error
     long read(uint8_t* dst, size_t n)
     {
@@ -648,6 +912,8 @@ struct GzStream {
 // parallel pread slices, gzip through a GzStream (inflated ahead, BGZF in
 // parallel).
 int g_gz_workers = 8;   // inflate threads per BGZF input (-t / 2 for PE)
+int g_gpu_inflate_dev = -1;   // --gpu-inflate: the device that inflates BGZF inputs
+bool g_gz_verbose = false;
 
 struct Input {
     int fd = -1;
@@ -662,6 +928,9 @@ struct Input {
         is_gz = ::pread(fd, m, 2, 0) == 2 && m[0] == 0x1f && m[1] == 0x8b;
         if (is_gz) {
             gz.reset(new GzStream());
+            gz->gpu_device = g_gpu_inflate_dev;
+            gz->verbose = g_gz_verbose;
+            gz->name = path;
             gz->start(fd, g_gz_workers);
         }
         return true;
@@ -1400,7 +1669,7 @@ struct Options {
     const char *f1 = nullptr, *f2 = nullptr, *out = nullptr, *arc = nullptr, *ref = nullptr;
     bool compress = false, decompress = false, index = false, force = false, in_dir = false, share_device = false,
          verbose = false, host_only = false, host_parse = false, ingest_only = false, ramp = false,
-         release = false, stage_ahead = false, shm = false, maxmis_set = false, ingest_crc = false;
+         release = false, stage_ahead = false, shm = false, maxmis_set = false, ingest_crc = false, gpu_inflate = false;
     // --read-threads: the plain-file reader's fill threads (SegReader).  16 since
     // round 6: the whole-node ingest (--ingest-only --devices 8) 34.3 / 35.8
     // against 18.2 / 28.7 GB/s with 8 (r6s; the reader two or three batches
@@ -1707,6 +1976,8 @@ int compress(const Options& o)
     const bool pe = o.f2 && *o.f2;
     // inflate threads per BGZF input: the -t share (the device parse leaves the host threads free)
     g_gz_workers = std::max(2, (o.threads > 0 ? o.threads : 16) / (pe ? 2 : 1));
+    g_gpu_inflate_dev = o.gpu_inflate ? o.device : -1;
+    g_gz_verbose = o.verbose;
     Input in1, in2;
     struct stat sb;
     for (const char* f : {o.f1, pe ? o.f2 : nullptr}) {
@@ -3080,6 +3351,7 @@ int main(int argc, char** argv)
         else if (!strcmp(a, "--host-only")) o.host_only = true;
         else if (!strcmp(a, "--ingest-only")) o.ingest_only = true;
         else if (!strcmp(a, "--ingest-crc")) o.ingest_crc = true;
+        else if (!strcmp(a, "--gpu-inflate")) o.gpu_inflate = true;
         else if (!strcmp(a, "--read-threads")) { if (!ival(o.read_threads, 0)) return usage(); }
         else if (!strcmp(a, "--writers")) { if (!ival(o.writers, 1)) return usage(); }
         else if (!strcmp(a, "--no-ramp")) o.ramp = false;

@@ -412,6 +412,51 @@ sa_hash_index *sa_hash_load(sa_ctx *ctx, const uint8_t *file, uint64_t bytes);
  * out has room for (bases + 15) / 16 words */
 int sa_hash_packed(sa_ctx *ctx, const sa_hash_index *ix, uint32_t *out, uint64_t words);
 
+/* ---- BGZF inflate on the device ------------------------------------------
+ * bgzip's BGZF is a series of gzip members of at most 64 KiB of text each, every
+ * one an independent raw-DEFLATE stream whose compressed size is in its 'BC'
+ * extra field and whose CRC-32 and ISIZE are in its trailer.  sa_bgzf_scan walks
+ * the members of a buffer on the host; sa_inflate_members inflates them on the
+ * device, one wave per member (k_inflate_bgzf), and checks each one's CRC. */
+typedef struct { uint64_t in_off; uint32_t in_len; uint64_t out_off; uint32_t isize; uint32_t crc; } sa_bgzf_member;
+/* per-member status of sa_inflate_members */
+enum {
+    SA_INFL_OK = 0,
+    SA_INFL_INPUT = 1,   /* the deflate stream runs past the member's compressed bytes */
+    SA_INFL_BLOCK = 2,   /* block type 3, or a stored block's LEN != ~NLEN              */
+    SA_INFL_CODES = 3,   /* code lengths zlib rejects, or a code that stands for nothing */
+    SA_INFL_DIST = 4,    /* a match reaches back past the member's first byte           */
+    SA_INFL_SIZE = 5,    /* the stream's output is not ISIZE bytes                      */
+    SA_INFL_CRC = 6      /* the output's CRC-32 is not the trailer's                    */
+};
+/* host: walk whole members in buf[0..have); *consumed = bytes of whole members, *out_bytes = sum of ISIZE.
+ * ms[i].in_off / in_len: the member's deflate bytes in buf; out_off: the sum of the ISIZEs before it.
+ * Returns the number of members (a member cut by the end of buf is left: *consumed < have), or
+ * <0: not BGZF / malformed header (-1), member larger than the format allows (-2), more than
+ * max_members (-3) */
+int64_t sa_bgzf_scan(const uint8_t *buf, uint64_t have, sa_bgzf_member *ms, uint64_t max_members,
+                     uint64_t *consumed, uint64_t *out_bytes);
+typedef struct sa_inflater sa_inflater;
+sa_inflater *sa_inflater_create(int device);          /* own stream and device slabs; no sa_ctx needed */
+void sa_inflater_destroy(sa_inflater *);
+/* H2D of in[0..in_bytes), kernel, D2H into out[0..out_bytes); status may be NULL.
+ * Every member is checked on the host first (in_off + in_len <= in_bytes, out_off + isize <=
+ * out_bytes, isize <= 65536): a bad descriptor is a call error and nothing is launched.  A
+ * member of isize 0 (the end-of-file marker) is ok when its crc is 0.  The copies are DMAs
+ * when in / out are sa_host_alloc memory and work from pageable memory too.
+ * All of out[0..out_bytes) is overwritten: the ranges of failed members, and any gaps the
+ * caller leaves between the members' ranges, with undefined bytes (the device slab is not
+ * cleared between calls).
+ * 0: every member ok; >0: number of failed members (status[i] says why); <0: call error */
+int sa_inflate_members(sa_inflater *, const uint8_t *in, uint64_t in_bytes, const sa_bgzf_member *ms,
+                       uint32_t n, uint8_t *out, uint64_t out_bytes, uint32_t *status);
+const char *sa_inflater_error(const sa_inflater *);
+float sa_inflater_kernel_ms(const sa_inflater *);      /* HIP events around the last kernel */
+/* (tests and diagnostics only) workgroups (one wave each) a launch uses at most: two per CU, or
+ * env SA_INFL_GRID (a small value makes every wave take many members), read at
+ * sa_inflater_create; lets a test assert that the knob took effect */
+uint32_t sa_inflater_grid(const sa_inflater *);
+
 #ifdef __cplusplus
 }
 #endif
