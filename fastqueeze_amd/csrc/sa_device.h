@@ -186,4 +186,16 @@ struct AsmView {
 constexpr uint32_t ASM_MAX_COPIES = 20;
 constexpr uint32_t ASM_COPY_WORDS = 1 + 3 * ASM_MAX_COPIES;
 
+// The engine's device error / counter buffer (sa_ctx::d_err), ERR_BYTES
+// cleared at the start of every batch: the error bits in words
+// [0, ERR_WORDS), then the counters work is taken from (the kernels get plain
+// pointers to them).
+constexpr uint32_t ERR_WORDS = 4;
+constexpr uint32_t ERR_WQ_PREP = 8;    // the front kernels' reads (WaveReads): k_prep_sq16
+constexpr uint32_t ERR_WQ_EMIT = 9;    // ... k_emit_sq16
+constexpr uint32_t ERR_WQ_DEGE = 10;   // k_emit_sq's listed reads
+constexpr uint32_t ERR_WQ_SPEC = 11;   // k_rb_spec's chunks
+constexpr size_t ERR_BYTES = 64;
+static_assert((ERR_WQ_SPEC + 1) * sizeof(uint32_t) <= ERR_BYTES, "a counter word outside the bytes a batch clears");
+
 }  // namespace sa

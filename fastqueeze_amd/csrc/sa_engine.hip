@@ -187,33 +187,28 @@ struct sa_input {
 };
 
 struct sa_ctx {
+    const EngineKnobs knobs;   // every SA_* knob read when the context is created (sa_knobs.h)
+    explicit sa_ctx(const EngineKnobs& k) : knobs(k), aux_dense(k.aux_dense), timing(k.trace) {}
+
     int device = 0;
-    // main/AUX, MD5, SEQ path (CU-masked), long AUX runs (CU-masked, disjoint)
-    hipStream_t st = nullptr, st2 = nullptr, st3 = nullptr, st4 = nullptr;
-    // SA_L_CU_EVERY=N (N >= 2): the L passes of the coder (L1 / L2 / L3) on a
-    // stream of their own, masked to every N-th CU, after the host has seen
-    // pass R end (the L passes are throughput kernels: on pass R's CUs they
-    // take the whole GPU for ~40 ms per batch and the other batches' front
-    // kernels beside them run ~3x slower, round 4 r4c trace).  0: after pass R
-    // on its stream (st3).
-    hipStream_t st5 = nullptr;
-    hipEvent_t ev_r_done = nullptr;
+    // main/AUX, MD5, SEQ path (CU-masked), long AUX runs (CU-masked, disjoint);
+    // st5: the L passes' own stream (SA_L_CU_EVERY, else null: st3)
+    hipStream_t st = nullptr, st2 = nullptr, st3 = nullptr, st4 = nullptr, st5 = nullptr;
     // (round 6) sa_text_upload's copies: a stream of their own, made on first
     // use (from whichever thread uploads), so the next batch's texts go to the
     // device while this context's kernels run
     hipStream_t st_copy = nullptr;
     std::mutex copy_mu;
-    // the dense AUX sort (k_aux_presence / k_aux_dense: one 9-bit pass over the
-    // blocks' dense model ids instead of two over the 17-bit ids).  The emit's
-    // target buffer depends on the number of passes, so the batch follows this
-    // context's previous one: a batch with more than 512 models in a block sorts
-    // in two dense passes and a copy, and turns it off.  SA_AUX_DENSE=0: off.
-    bool aux_dense = !(std::getenv("SA_AUX_DENSE") && std::atoi(std::getenv("SA_AUX_DENSE")) == 0);
+    // the dense AUX sort's flag (EngineKnobs::aux_dense to begin with).  The
+    // emit's target buffer depends on the number of passes, so the batch follows
+    // this context's previous one: a batch with more than 512 models in a block
+    // sorts in two dense passes and a copy, and turns it off.
+    bool aux_dense;
     DBuf d_aux_bm, d_aux_tab, d_aux_nmod;
     uint32_t* h_aux_nmod = nullptr;   // (pinned)
     size_t h_aux_nmod_cap = 0;
-    hipEvent_t ev_dense = nullptr;
-    hipEvent_t ev_fork = nullptr, ev_fork_seq = nullptr, ev_md5_done = nullptr, ev_r[2] = {nullptr, nullptr};
+    hipEvent_t ev_r_done = nullptr, ev_dense = nullptr;
+    hipEvent_t ev_fork = nullptr, ev_fork_seq = nullptr, ev_md5_done = nullptr;
     hipEvent_t ev_seq_done = nullptr, ev_long_done = nullptr;
     // the AUX record array is all zero between batches (pass R's unwritten-record
     // test): zeroed in the tail of the batch that used it (st3, after the L
@@ -223,116 +218,13 @@ struct sa_ctx {
     size_t prs_zero_cap = 0;
     void* prs_zero_p = nullptr;
     bool prs_zero_pending = false;
-    uint32_t long_lds = 0;
     bool front_masked = false;   // (SA_RV_CUS: the front's stream on the CUs pass R leaves)
-    uint32_t chain_prio = 1;   // s_setprio 3 in the latency-bound chain kernels (SA_CHAIN_PRIO=0: off)
-    uint32_t md5_prio = 1;     // ... and in k_md5 (SA_MD5_PRIO; off the critical path)
-    bool prep_fused = std::getenv("SA_PREP_FUSED") != nullptr;   // name columns in k_prep_sq16 (A/B)
-    bool prep_wave = std::getenv("SA_PREP_WAVE") != nullptr;   // k_prep_sq instead of k_prep_sq16
-    bool emit_wave = std::getenv("SA_EMIT_WAVE") != nullptr;
     uint32_t reserve_blocks = 0;   // sa_set_reserve: the batch size to allocate for
     bool front_warm = false;       // a batch ran: its buffers exist (run_input's `early`)
-    // records per chunk in the L passes (SA_L_CHUNK=16: 56 VGPRs, 8 waves per
-    // SIMD, half a line per chunk; 32: 88 VGPRs, 5 waves, a whole line)
-    uint32_t l_chunk = std::getenv("SA_L_CHUNK") && std::atoi(std::getenv("SA_L_CHUNK")) == 16 ? 16u : 32u;
-    // the L passes at issue priority 2 (they are on the batch's critical path,
-    // the other contexts' fronts beside them are not always; SA_L_PRIO=1, A/B)
-    uint32_t l_prio = std::getenv("SA_L_PRIO") && std::atoi(std::getenv("SA_L_PRIO")) != 0 ? 1u : 0u;
-    bool seq_unpacked = std::getenv("SA_SEQ_PACK") && std::atoi(std::getenv("SA_SEQ_PACK")) == 0;
-    // k_prep_sq16 / k_emit_sq16 with the round-4 static grid stride instead of
-    // reads taken from a counter (WaveReads; SA_FRONT_STATIC=1, A/B)
-    bool front_static = std::getenv("SA_FRONT_STATIC") && std::atoi(std::getenv("SA_FRONT_STATIC")) != 0;
-    // reads a front wave takes from the counter at a time (WaveReads): 0 = by the
-    // batch's mean read length (front_wq_chunk), SA_WQ_CHUNK=n to fix it (A/B;
-    // 64 was the only value until round 6)
-    uint32_t wq_chunk_env = std::getenv("SA_WQ_CHUNK") ? (uint32_t)std::atoi(std::getenv("SA_WQ_CHUNK")) : 0u;
-    // pass R with one chain per lane in the VALU (k_coder_rl: the scalar units
-    // stay free for the front kernels of the other batches) instead of one
-    // chain per wave on the scalar unit (k_coder_rv); SA_RV_LANES=1 / 0.  Off:
-    // pass R 1,835-1,864 against 679-689 ms under the bench's load, the bench
-    // 7,971-8,064 against 16,849-16,908 MB/s (r5k)
-    bool rv_lanes = std::getenv("SA_RV_LANES") && std::atoi(std::getenv("SA_RV_LANES")) != 0;
-    // the SEQ space sorted by the context's low 8-9 bits only and replayed per
-    // bucket with the models in LDS (k_replay_seq_bkt, contexts of <= 22 bits);
-    // SA_SEQ_BUCKET=0: the full sort and k_replay_seq.  By the low bits the
-    // bench gained 1-3 % (r5k: 17,039 / 17,349 against 16,908 / 16,849 MB/s,
-    // SEQ sort + replay 84 against 88-98 ms); by the top bits it had lost
-    // (r5e-r5h: 14.9-15.4 against 15.9-16.8 GB/s)
-    bool seq_bucket = !(std::getenv("SA_SEQ_BUCKET") && std::atoi(std::getenv("SA_SEQ_BUCKET")) == 0);
-    // the bucket replay's records in sorted order (coalesced stores), then put
-    // in stream order by a gather through the sort's inverse permutation, which
-    // the bucket pass writes in stream order instead of the positions
-    // (k_seq_unpermute); SA_SEQ_INV=0: one scattered 4-byte store per symbol
-    bool seq_inv = !(std::getenv("SA_SEQ_INV") && std::atoi(std::getenv("SA_SEQ_INV")) == 0);
-    // SA_BKT_DB=8 / 9 / 10: the bucket pass's digit bits (default 8 for contexts
-    // of <= 20 bits, 9 above; 10 with the inverse-permutation pass only)
-    int bkt_db_env = std::getenv("SA_BKT_DB") ? std::atoi(std::getenv("SA_BKT_DB")) : 0;
-    int prep_row = std::getenv("SA_PREP_ROW") ? std::atoi(std::getenv("SA_PREP_ROW")) : 0;
-    // the bucket replay's largest digits first (k_bkt_order); SA_BKT_LPT=0: digit order
-    bool bkt_lpt = !(std::getenv("SA_BKT_LPT") && std::atoi(std::getenv("SA_BKT_LPT")) == 0);
-    // SA_BKT_PROBE=file: per bucket-replay wave its clocks and steps, appended
-    // to file (the front waits for the replay to read them back: diagnostics)
-    const char* bkt_probe = std::getenv("SA_BKT_PROBE");
-    DBuf d_bkt_probe;
-    // workgroups per CU of the grid-stride wave-per-read kernels (SA_WAVE_GRID)
-    uint32_t wg_per_cu = std::getenv("SA_WAVE_GRID") ? (uint32_t)std::max(1, std::atoi(std::getenv("SA_WAVE_GRID"))) : 8u;
-    // k_md5<true> reads the next block's words while the chain runs: 148 VGPRs instead
-    // of 60, which costs the co-resident front kernels more than it saves (r2x:
-    // 11.6 vs 12.9 GB/s), so SA_MD5_PIPE=1 only
-    bool md5_pipe = std::getenv("SA_MD5_PIPE") && std::atoi(std::getenv("SA_MD5_PIPE")) != 0;
-    // pass-R placement (k_coder_rv): four chains per workgroup, one per SIMD, and
-    // enough unused LDS that a CU holds one pass-R workgroup (SA_CODER_WAVES /
-    // SA_CODER_LDS)
-    // The waits between this context's streams happen on the host thread (which
-    // has nothing else to do then) instead of as barrier packets: the boxes run
-    // with four hardware queues per process (GPU_MAX_HW_QUEUES=4), so the
-    // contexts' streams share queues, and a barrier waiting for this batch's
-    // front or long runs held up every other context's work queued behind it
-    // (pass R, L passes).  SA_HOST_WAITS=0: device-side waits, for A/B.
-    bool host_waits = !(std::getenv("SA_HOST_WAITS") && std::atoi(std::getenv("SA_HOST_WAITS")) == 0);
-    uint32_t coder_waves = 4;
-    // the pass-R step order (k_coder_rv<V>): 5 = the 24 v_readlane of eight steps
-    // issued together ahead of their SALU steps (r4z3: pass R 671-675 against
-    // 767-776 ms, the bench +3-5 %); 0 = a step's three v_readlane ahead of it.
-    // The batched moves hold the vector unit of their SIMD longer, and batches
-    // of long reads (mean > 1000 bp), whose fronts are VALU-heavy and set the
-    // pace, ran 11 % slower with them (r4z5: ONT shape 7,187 / 7,281 against
-    // 8,081 / 8,260 MB/s), so those keep 0.  SA_RV_VARIANT=0 / 5: one for all.
-    // Round 6: 6 = the operands through SMEM from a per-wave ring the lanes fill
-    // (k_coder_rv<6>, coder_rg_chain): the chain itself is faster (r6b: one
-    // context alone 504 against 630 ms; under the bench's load 626-644 against
-    // 665-691) but it issues 10 SALU per symbol instead of 8 and holds its SIMD's
-    // scalar issue ~90 % of the time, so the kernels that share those SIMDs
-    // slow (L passes 89 against 52 ms, prep 16 against 10) and the bench lost
-    // 3 % (r6b / r6c: 16,623-16,904 against 17,281-17,493 MB/s).  On the tree
-    // with the full-segment L passes the bench is level (r6m: 19,301 / 19,237
-    // against 19,437 / 19,279) and the command line, whose batches' latency
-    // sets its pace, faster: 42.8 GB in 3.47 / 3.53 s against 4.22 / 3.89 s
-    // (r6o); and in r6q the bench too (19,339 / 19,422 against 18,386 /
-    // 18,851 MB/s), so 6 is the default for short-read batches since round 6.
-    int rv_variant = std::getenv("SA_RV_VARIANT") ? std::atoi(std::getenv("SA_RV_VARIANT")) : -1;
-    // (default variant, A/B) 6 only while at most SA_RV_V6_MAX other contexts of
-    // the device are in pass R, else 5; -1: 5 always.  Unset: 6 always -- the
-    // limit measured no better (r6q: bench 19,106 / 19,264 with 2, 18,386 /
-    // 18,851 with -1, 19,339 / 19,422 without; 42.8 GB in 5.02 / 4.28 s with 2,
-    // 4.44 / 4.11 with -1, 4.35 / 4.17 without)
-    int rv_v6_max = std::getenv("SA_RV_V6_MAX") ? std::atoi(std::getenv("SA_RV_V6_MAX")) : 1 << 30;
-    int rv_batch = 5;   // the current batch's (run_input)
-    // pass R's wait for records the long runs have not written (SA_RV_WAIT_MS, default 20 s: the
-    // long runs take ~0.4 s; a wave that waits longer gives up and the batch fails with E_CODER)
-    uint32_t rv_wait_ticks = std::getenv("SA_RV_WAIT_MS")
-                                 ? (uint32_t)std::min<uint64_t>(100000ull * (uint64_t)std::max(1, std::atoi(std::getenv("SA_RV_WAIT_MS"))),
-                                                                4000000000ull)
-                                 : 2000000000u;
-    bool test_skip_long = std::getenv("SA_TEST_SKIP_LONG") != nullptr;   // (tests: starve pass R)
-    uint32_t rv_short_waves = std::getenv("SA_RV_SHORT_WAVES") ? (uint32_t)std::atoi(std::getenv("SA_RV_SHORT_WAVES")) : 32u;
-    // k_replay_aux_long workgroups: what the long-run CUs hold at once (6 per CU;
-    // SA_LONG_GRID overrides, round 2 used 2048)
-    uint32_t long_grid = 0;
-    uint32_t coder_lds = 82 * 1024;
+    int rv_batch = 5;   // the current batch's pass-R variant (PathPlan::rv_batch, SA_RV_V6_MAX)
+    uint32_t long_grid = 0;   // k_replay_aux_long workgroups (EngineKnobs::long_grid_env)
     std::string err;
-    bool timing = false;
-    bool trace = std::getenv("SA_TRACE") != nullptr;
+    bool timing;
     // pinned host mailbox for the run's small copies (plans, task lists, count
     // and length read-backs): a pageable copy goes through the runtime's
     // staging path, which the other contexts' bulk copies hold up; bump
@@ -354,10 +246,7 @@ struct sa_ctx {
     hipEvent_t ev_beg[PH_N] = {}, ev_end[PH_N] = {};
     float ph_ms[PH_N];
     float align_kernel_ms = 0.f;   // sa_hash_align: the aligner kernel of the last call (variant 0)
-    // SA_RV_PROBE=file: per pass-R wave its timing and placement, appended to
-    // the file per batch (diagnostics, k_coder_rv)
-    const char* rv_probe = std::getenv("SA_RV_PROBE");
-    DBuf d_probe;
+    DBuf d_bkt_probe, d_probe;   // SA_BKT_PROBE / SA_RV_PROBE
     uint32_t probe_waves = 0;
     DBuf d_ring;   // pass R's per-wave operand rings (k_coder_rv<6>)
 
@@ -378,25 +267,6 @@ struct sa_ctx {
     DBuf d_dege_list;   // the reads with N / IUPAC bases (k_dege_list -> k_emit_sq)
     DBuf d_qual_q, d_rb_chunks, d_rb_ck0, d_rb_opens, d_rb_spec, d_rb_entry, d_rb_guess, d_rb_tab;   // -l (rblock)
     DBuf d_rb_vals, d_rb_info;   // (round 5: run values per chunk byte, RbInfo per chunk)
-    // SA_RB_APPLY=1: the round-4 second full walk (k_rb_apply) instead of k_rb_true + k_rb_fill (A/B)
-    bool rb_apply_walk = std::getenv("SA_RB_APPLY") && std::atoi(std::getenv("SA_RB_APPLY")) != 0;
-    // SA_RB_FIX_SERIAL=1: the entries by k_rb_fix (a lane per block, chunk by
-    // chunk) instead of k_rb_fix_w (a wave per block, 64 chunks a step; A/B)
-    bool rb_fix_serial = std::getenv("SA_RB_FIX_SERIAL") && std::atoi(std::getenv("SA_RB_FIX_SERIAL")) != 0;
-    // k_rb_spec on n workgroups per CU taking 64 chunks at a time from a
-    // counter (round 6: n = 2, the ONT batch's prep+scan 25.0 / 26.4 against
-    // 28.6 / 29.7 ms with one grid of a lane per chunk, r6z8; 4: no gain);
-    // SA_RB_SPEC_WG=n to change, 0 = the one grid
-    uint32_t rb_spec_wg = std::getenv("SA_RB_SPEC_WG") ? (uint32_t)std::max(0, std::atoi(std::getenv("SA_RB_SPEC_WG"))) : 2u;
-    // R-Block chunk length, also the stride of the per-chunk arrays (opens,
-    // vals): SA_RB_CHUNK=n, a multiple of 32 up to RB_CHUNK.  Not a power of
-    // two: the lanes of k_rb_spec walk their chunks in step, so at 8192 every
-    // lane's load and store of a step fell on addresses 8 KiB apart (round 6)
-    uint32_t rb_chunk = [] {
-        const char* e = std::getenv("SA_RB_CHUNK");
-        const uint32_t n = e ? (uint32_t)std::atoi(e) : RB_CHUNK_DEFAULT;
-        return n >= 32 && n <= RB_CHUNK && n % 32 == 0 ? n : RB_CHUNK;
-    }();
     std::vector<uint32_t> rb_tab_host;   // the R decision tables (RbTab) of rb_tab_r
     double rb_tab_r = -1.0;
     bool rb_tab_sent = false;
@@ -417,8 +287,9 @@ struct sa_ctx {
     // last run
     std::vector<uint64_t> final_base, final_len;
     bool have_output = false;
-    // what the host chose for the last run (sa_last_paths): filled where the
-    // launches are chosen; paths_r: pass R's first launch of the run is in it
+    // what the host chose for the last run (sa_last_paths): report_paths from
+    // the plan, the rest where the device's answer is known; paths_r: pass R's
+    // first launch of the run is in it
     sa_paths paths{};
     bool paths_r = false;
 
@@ -440,6 +311,23 @@ struct sa_ctx {
         for (DBuf* b : work_buffers()) h += b->cap;
         return h;   // (the front scratch: front_bytes)
     }
+    // every event of the context (created by sa_create, destroyed here); timed: a phase's
+    struct Ev {
+        hipEvent_t* e;
+        bool timed;
+    };
+    std::vector<Ev> events()
+    {
+        std::vector<Ev> v;
+        for (hipEvent_t* e : {&ev_fork, &ev_fork_seq, &ev_md5_done, &ev_seq_done, &ev_long_done, &ev_prs_zero, &ev_r_done,
+                              &ev_dense})
+            v.push_back(Ev{e, false});
+        for (int i = 0; i < PH_N; i++) {
+            v.push_back(Ev{&ev_beg[i], true});
+            v.push_back(Ev{&ev_end[i], true});
+        }
+        return v;
+    }
 
     ~sa_ctx()
     {
@@ -452,24 +340,13 @@ struct sa_ctx {
             }
             fs = nullptr;
         }
-        std::vector<DBuf*> all = work_buffers();
-        for (DBuf* b : all) b->release();
-        for (int i = 0; i < PH_N; i++) {
-            if (ev_beg[i]) (void)hipEventDestroy(ev_beg[i]);
-            if (ev_end[i]) (void)hipEventDestroy(ev_end[i]);
-        }
-        for (hipEvent_t e : {ev_fork, ev_fork_seq, ev_md5_done, ev_r[0], ev_r[1], ev_seq_done, ev_long_done, ev_prs_zero})
-            if (e) (void)hipEventDestroy(e);
+        for (DBuf* b : work_buffers()) b->release();
+        for (const Ev& ev : events())
+            if (*ev.e) (void)hipEventDestroy(*ev.e);
         if (mail) (void)hipHostFree(mail);
         for (uint8_t* m : mail_retired) (void)hipHostFree(m);
-        if (st) (void)hipStreamDestroy(st);
-        if (st2) (void)hipStreamDestroy(st2);
-        if (st3) (void)hipStreamDestroy(st3);
-        if (st4) (void)hipStreamDestroy(st4);
-        if (st5) (void)hipStreamDestroy(st5);
-        if (st_copy) (void)hipStreamDestroy(st_copy);
-        if (ev_r_done) (void)hipEventDestroy(ev_r_done);
-        if (ev_dense) (void)hipEventDestroy(ev_dense);
+        for (hipStream_t s : {st, st2, st3, st4, st5, st_copy})
+            if (s) (void)hipStreamDestroy(s);
         if (h_aux_nmod) (void)hipHostFree(h_aux_nmod);
     }
 };
@@ -545,58 +422,40 @@ hipError_t sync_d2h(sa_ctx* c, hipStream_t st)
     return e;
 }
 
-// Reads per take of the front kernels' read counter: ~64 reads' worth of
-// 150 bp (about 10 KB of bases) a take, so short-read batches keep WQ_CHUNK
-// and long-read batches take one wave's four reads at a time; a multiple of
-// four (the rows of a wave).
-uint32_t front_wq_chunk(const sa_ctx* c, uint64_t seq_bytes, uint32_t nreads)
+// sa_knobs.h's copies of the kernels' constants
+static_assert(host_k::SORT_MIN_DB == SORT_MIN_DB && host_k::SORT_MAX_DB == SORT_MAX_DB &&
+                  host_k::WQ_CHUNK == WQ_CHUNK && host_k::KEY_SLACK == KEY_SLACK &&
+                  host_k::AUX_DENSE_BITS == AUX_DENSE_BITS && host_k::SEQ_HALVE_J == SEQ_HALVE_J &&
+                  host_k::LONG_RUN == LONG_RUN && host_k::RB_CHUNK == RB_CHUNK &&
+                  host_k::RB_CHUNK_DEFAULT == RB_CHUNK_DEFAULT,
+              "sa_knobs.h: host_k differs from the kernels' constants");
+
+// ---- the environment: read here and nowhere else (and SA_SYNC in sa_create) ----
+const char* env_get(const char* name) { return std::getenv(name); }
+
+int sort_min_db()   // SA_SORT_MIN_DB: once per process
 {
-    if (c->wq_chunk_env) return std::max<uint32_t>(4, std::min<uint32_t>(1024, c->wq_chunk_env & ~3u));
-    const uint64_t mean = nreads ? std::max<uint64_t>(1, seq_bytes / nreads) : 1;
-    const uint64_t k = (uint64_t)WQ_CHUNK * 150 / mean;
-    return (uint32_t)std::max<uint64_t>(4, std::min<uint64_t>(WQ_CHUNK, k) & ~3ull);
+    static const int v = parse_sort_min_db(env_get);
+    return v;
 }
+
+RunKnobs run_knobs() { return parse_run_knobs(env_get, sort_min_db()); }
 
 // grid of a wave-per-read, grid-stride kernel (EMIT_WAVES waves per workgroup):
 // 8 workgroups per CU, fewer for a small batch
 uint32_t wave_grid(const sa_ctx* c, uint32_t nreads)
 {
-    return std::max<uint32_t>(1, std::min<uint32_t>((nreads + EMIT_WAVES - 1) / EMIT_WAVES, c->wg_per_cu * c->n_cu));
+    return std::max<uint32_t>(1, std::min<uint32_t>((nreads + EMIT_WAVES - 1) / EMIT_WAVES, c->knobs.wg_per_cu * c->n_cu));
 }
 
-// Digit widths of a sort over bits [lo, hi): the fewest passes of at most
-// SORT_MAX_DB bits, widths as even as possible and at least SORT_MIN_DB (a
-// digit may reach above hi: those key bits are 0, or 1 in the pad keys, which
-// sort last anyway).
+// sa_plan.h's sort_digits / sort_hist_per_tile with the process's SA_SORT_MIN_DB
 std::vector<int> sort_digits(int lo, int hi, int max_db = SORT_MAX_DB)
 {
-    std::vector<int> w;
-    if (hi <= lo) return w;
-    static const int min_db = std::getenv("SA_SORT_MIN_DB") ? std::max(7, std::min(9, std::atoi(std::getenv("SA_SORT_MIN_DB"))))
-                                                           : SORT_MIN_DB;
-    const int bits = hi - lo, passes = (bits + max_db - 1) / max_db;
-    for (int p = 0, done = 0; p < passes; p++) {
-        const int d = (bits - done + (passes - p) - 1) / (passes - p);
-        w.push_back(std::max(d, min_db));
-        done += d;
-    }
-    return w;
+    return sa::sort_digits(lo, hi, max_db, sort_min_db());
 }
-
-// the digit widths of a sort, first pass in the low four bits (sa_paths)
-uint32_t pack_digits(const std::vector<int>& w)
-{
-    uint32_t p = 0;
-    for (size_t i = 0; i < w.size() && i < 8; i++) p |= (uint32_t)w[i] << (4 * i);
-    return p;
-}
-
-// histogram words per tile of a sort over bits [lo, hi)
 uint64_t sort_hist_per_tile(int lo, int hi, int max_db = SORT_MAX_DB)
 {
-    int m = 0;
-    for (int d : sort_digits(lo, hi, max_db)) m = std::max(m, d);
-    return 1ull << m;
+    return sa::sort_hist_per_tile(lo, hi, max_db, sort_min_db());
 }
 
 template <int DB>
@@ -696,15 +555,15 @@ void ev_finish(sa_ctx* c, int ph, hipStream_t st);
 // d_qual_q, which the QUAL stream then codes (speculative chunks, one carry
 // lane per block, chunk replay; sa_logic.h).  The staged qualities stay
 // untouched: the N/IUPAC side streams use them, and the batch can be re-run.
-int run_rblock(sa_ctx* c, double ratio, uint64_t seq_bytes, BatchView& bv)
+int run_rblock(sa_ctx* c, const PathPlan& K, double ratio, uint64_t seq_bytes, BatchView& bv)
 {
     hipStream_t st = c->st;
     std::vector<RbChunk> ck;
     std::vector<uint32_t> ck0;
     for (const DevBlock& d : c->blocks) {
         ck0.push_back((uint32_t)ck.size());
-        for (uint64_t o = 0; o < d.seq_bytes; o += c->rb_chunk) {
-            const uint32_t len = (uint32_t)std::min<uint64_t>(c->rb_chunk, d.seq_bytes - o);
+        for (uint64_t o = 0; o < d.seq_bytes; o += K.rb_chunk) {
+            const uint32_t len = (uint32_t)std::min<uint64_t>(K.rb_chunk, d.seq_bytes - o);
             uint32_t fl = (o == 0 ? RB_FIRST : 0u) | (o + len == d.seq_bytes ? RB_LAST : 0u);
             ck.push_back(RbChunk{d.seq_base + o, len, fl});
         }
@@ -735,30 +594,25 @@ int run_rblock(sa_ctx* c, double ratio, uint64_t seq_bytes, BatchView& bv)
         SA_CHECK(c, h2d(c, c->d_rb_tab.p, c->rb_tab_host.data(), 8ull * RB_TAB_WORDS, st));
         c->rb_tab_sent = true;
     }
-    c->paths.rblock = 1;
-    c->paths.rb_spec_counter = c->rb_spec_wg > 0 ? 1u : 0u;
-    c->paths.rb_fix_wave = c->rb_fix_serial ? 0u : 1u;
-    c->paths.rb_apply_walk = c->rb_apply_walk ? 1u : 0u;
-    c->paths.rb_chunk = c->rb_chunk;
     const uint32_t* tab = c->d_rb_tab.as<uint32_t>();
     const RbChunk* dck = c->d_rb_chunks.as<RbChunk>();
     const uint32_t rgrid = (nck + RB_THREADS - 1) / RB_THREADS;
-    const bool walk = c->rb_apply_walk;
+    const bool walk = K.rb_apply_walk;
     if (!walk) {
         SA_CHECK(c, c->d_rb_vals.ensure((uint64_t)RB_CHUNK * nck));
         SA_CHECK(c, c->d_rb_info.ensure(sizeof(RbInfo) * nck));
     }
     uint8_t* vals = walk ? nullptr : c->d_rb_vals.as<uint8_t>();
     RbInfo* info = walk ? nullptr : c->d_rb_info.as<RbInfo>();
-    const uint32_t cs = c->rb_chunk;   // (the arrays' stride per chunk: bytes, opens words * 32)
+    const uint32_t cs = K.rb_chunk;   // (the arrays' stride per chunk: bytes, opens words * 32)
     // (rb_spec_wg workgroups per CU taking chunks from a counter; 0: one grid)
-    uint32_t* wq_spec = c->rb_spec_wg > 0 ? c->d_err.as<uint32_t>() + 11 : nullptr;
-    const uint32_t sgrid = wq_spec ? std::max<uint32_t>(1, std::min<uint32_t>(rgrid, c->rb_spec_wg * c->n_cu)) : rgrid;
+    uint32_t* wq_spec = K.rb_spec_wg > 0 ? c->d_err.as<uint32_t>() + ERR_WQ_SPEC : nullptr;
+    const uint32_t sgrid = wq_spec ? std::max<uint32_t>(1, std::min<uint32_t>(rgrid, K.rb_spec_wg * c->n_cu)) : rgrid;
     hipLaunchKernelGGL(k_rb_spec, dim3(sgrid), dim3(RB_THREADS), 0, st, bv.qual, dck, nck, tab,
                        c->d_rb_opens.as<uint32_t>(), c->d_rb_spec.as<RbRun>(), vals, info, cs, wq_spec);
     hipLaunchKernelGGL(k_rb_guess, dim3(rgrid), dim3(RB_THREADS), 0, st, bv.qual, dck, nck, tab,
                        c->d_rb_opens.as<uint32_t>(), c->d_rb_spec.as<RbRun>(), c->d_rb_guess.as<RbRun>(), cs);
-    if (c->rb_fix_serial)
+    if (!K.rb_fix_wave)
         hipLaunchKernelGGL(k_rb_fix, dim3((nbk + 63) / 64), dim3(64), 0, st, bv.qual, dck, c->d_rb_ck0.as<uint32_t>(),
                            nbk, tab, c->d_rb_opens.as<uint32_t>(), c->d_rb_spec.as<RbRun>(),
                            c->d_rb_guess.as<RbRun>(), c->d_rb_entry.as<RbRun>(), cs);
@@ -825,46 +679,47 @@ constexpr uint32_t RV_LONG_SYMS = 1u << 21;
 int coder_launch_r(sa_ctx* c, hipStream_t st, TaskList tl, const CoderView& cv, int ph, uint32_t nlong)
 {
     if (!tl.count) return 0;
+    const EngineKnobs& K = c->knobs;
     uint32_t waves = tl.count;
     tl.nlong = tl.count;
-    if (c->rv_short_waves && nlong + c->rv_short_waves < tl.count) {
+    if (K.rv_short_waves && nlong + K.rv_short_waves < tl.count) {
         tl.nlong = nlong;
-        waves = nlong + c->rv_short_waves;
+        waves = nlong + K.rv_short_waves;
     }
     if (!c->paths_r) {   // (the run's first pass R; the restarts' lists are short)
         c->paths_r = true;
-        c->paths.pass_r = c->rv_lanes ? SA_PATH_R_LANES : c->rv_batch == 6 ? SA_PATH_R_V6 : c->rv_batch == 5 ? SA_PATH_R_V5 : SA_PATH_R_V0;
+        c->paths.pass_r = K.rv_lanes ? SA_PATH_R_LANES : c->rv_batch == 6 ? SA_PATH_R_V6 : c->rv_batch == 5 ? SA_PATH_R_V5 : SA_PATH_R_V0;
         c->paths.r_short_shared = tl.nlong != tl.count ? 1u : 0u;
-        c->paths.r_waves = c->rv_lanes ? (uint32_t)RL_WAVES : c->coder_waves;
-        c->paths.chain_prio = c->chain_prio;
+        c->paths.r_waves = K.rv_lanes ? (uint32_t)RL_WAVES : K.coder_waves;
+        c->paths.chain_prio = K.chain_prio;
     }
     if (ph >= 0) ev_begin(c, ph, st);
-    tl.wait_ticks = c->rv_wait_ticks;
-    if (c->rv_lanes) {   // a chain per lane, 64 per workgroup, longest first
+    tl.wait_ticks = K.rv_wait_ticks;
+    if (K.rv_lanes) {   // a chain per lane, 64 per workgroup, longest first
         hipLaunchKernelGGL(k_coder_rl, dim3((tl.count + 63) / 64), dim3(64 * RL_WAVES), 0, st, cv.tasks, tl, cv.prs[0],
-                           cv.prs[1], cv.ck_r, c->d_err.as<uint32_t>(), c->chain_prio);
+                           cv.prs[1], cv.ck_r, c->d_err.as<uint32_t>(), K.chain_prio);
         if (ph >= 0) ev_finish(c, ph, st);
         return 0;
     }
-    const uint32_t grid = (waves + c->coder_waves - 1) / c->coder_waves;
+    const uint32_t grid = (waves + K.coder_waves - 1) / K.coder_waves;
     uint64_t* probe = nullptr;
-    if (c->rv_probe && ph >= 0 && c->d_probe.ensure(32ull * grid * c->coder_waves) == hipSuccess) {
+    if (K.rv_probe && ph >= 0 && c->d_probe.ensure(32ull * grid * K.coder_waves) == hipSuccess) {
         probe = c->d_probe.as<uint64_t>();
-        c->probe_waves = grid * c->coder_waves;
+        c->probe_waves = grid * K.coder_waves;
         (void)hipMemsetAsync(probe, 0, 32ull * c->probe_waves, st);
     }
     // (V = 6) a 2 KiB ring per wave, sized for 1024 waves from the start (a
     // re-allocation's hipFree would synchronise the device)
     if (c->rv_batch == 6 &&
-        c->d_ring.ensure(4ull * RING_DW * std::max<uint32_t>(1024u, grid * c->coder_waves)) != hipSuccess) {
+        c->d_ring.ensure(4ull * RING_DW * std::max<uint32_t>(1024u, grid * K.coder_waves)) != hipSuccess) {
         c->err = "pass R: cannot allocate the operand ring";
         return -1;
     }
     hipLaunchKernelGGL(c->rv_batch == 6   ? k_coder_rv<6>
                        : c->rv_batch == 5 ? k_coder_rv<5>
                                           : k_coder_rv<0>,
-                       dim3(grid), dim3(64 * c->coder_waves), c->coder_lds, st, cv.tasks, tl, cv.prs[0], cv.prs[1],
-                       cv.ck_r, c->d_err.as<uint32_t>(), c->chain_prio, probe, c->d_ring.as<uint32_t>());
+                       dim3(grid), dim3(64 * K.coder_waves), K.coder_lds, st, cv.tasks, tl, cv.prs[0], cv.prs[1],
+                       cv.ck_r, c->d_err.as<uint32_t>(), K.chain_prio, probe, c->d_ring.as<uint32_t>());
     if (ph >= 0) ev_finish(c, ph, st);
     return 0;
 }
@@ -877,7 +732,7 @@ void write_rv_probe(sa_ctx* c, const std::vector<uint64_t>& p)
     static std::mutex mu;
     static uint64_t batch = 0;
     std::lock_guard<std::mutex> g(mu);
-    FILE* f = std::fopen(c->rv_probe, "a");
+    FILE* f = std::fopen(c->knobs.rv_probe, "a");
     if (!f) return;
     const uint64_t b = batch++;
     for (size_t w = 0; w + 3 < p.size(); w += 4) {
@@ -893,11 +748,34 @@ void write_rv_probe(sa_ctx* c, const std::vector<uint64_t>& p)
     std::fclose(f);
 }
 
+// SA_BKT_PROBE: reads the bucket replay's probe back (the front waits for the
+// replay: diagnostics) and appends one line per wave: block, digit (its rank
+// with k_bkt_order, `ranked`), start / end (us, 100 MHz), cycles, steps, shared
+// steps, xcc
+int dump_bkt_probe(sa_ctx* c, hipStream_t st, const uint64_t* bprobe, uint32_t bgrid, uint32_t nbk, int db, bool ranked)
+{
+    std::vector<uint64_t> pr(4ull * bgrid);
+    SA_CHECK(c, hipMemcpyAsync(pr.data(), bprobe, 32ull * bgrid, hipMemcpyDeviceToHost, st));
+    SA_CHECK(c, hipStreamSynchronize(st));
+    FILE* f = std::fopen(c->knobs.bkt_probe, "a");
+    if (!f) return 0;
+    for (uint32_t w = 0; w < bgrid; w++) {
+        const uint64_t* q = &pr[4ull * w];
+        if (!q[1]) continue;
+        std::fprintf(f, "%u %u %.2f %.2f %llu %llu %llu %llu\n", ranked ? w % nbk : w >> db,
+                     ranked ? w / nbk : w & ((1u << db) - 1), (double)q[0] / 100.0, (double)q[1] / 100.0,
+                     (unsigned long long)q[2], (unsigned long long)(q[3] & 0xffffff),
+                     (unsigned long long)((q[3] >> 24) & 0xffffff), (unsigned long long)(q[3] >> 48));
+    }
+    std::fclose(f);
+    return 0;
+}
+
 void coder_launch_l12(sa_ctx* c, hipStream_t st, const TaskList& tl, const CoderView& cv)
 {
     if (!tl.count) return;
     const uint32_t lgrid = (uint32_t)((tl.total_segs + 255) / 256);
-    hipLaunchKernelGGL(c->l_chunk == 16 ? k_coder_l1<16> : k_coder_l1<32>, dim3(lgrid), dim3(256), 0, st, cv, tl);
+    hipLaunchKernelGGL(c->knobs.l_chunk == 16 ? k_coder_l1<16> : k_coder_l1<32>, dim3(lgrid), dim3(256), 0, st, cv, tl);
     hipLaunchKernelGGL(k_coder_l2, dim3(tl.count), dim3(L2_THREADS), 0, st, cv, tl);
 }
 
@@ -905,7 +783,7 @@ void coder_launch_l3(sa_ctx* c, hipStream_t st, const TaskList& tl, const CoderV
 {
     if (!tl.count) return;
     const uint32_t lgrid = (uint32_t)((tl.total_segs + 255) / 256);
-    hipLaunchKernelGGL(c->l_chunk == 16 ? k_coder_l3<16> : k_coder_l3<32>, dim3(lgrid), dim3(256), 0, st, cv, tl);
+    hipLaunchKernelGGL(c->knobs.l_chunk == 16 ? k_coder_l3<16> : k_coder_l3<32>, dim3(lgrid), dim3(256), 0, st, cv, tl);
 }
 
 // Range coder driver (DESIGN.md "Coder"): pass R of every listed chain (on st,
@@ -919,13 +797,14 @@ void coder_launch_l3(sa_ctx* c, hipStream_t st, const TaskList& tl, const CoderV
 // does.  out_len: every stream's bytes.  Returns 0, -1 on error, 2 when a
 // stream outgrew its slack (the caller re-runs with exact = false).
 int coder_run(sa_ctx* c, std::vector<CoderTask>& tasks, CoderView& cv, hipStream_t st, int ph_r, int ph_l,
-              hipEvent_t before_l, bool exact, std::vector<uint32_t>& out_len, uint64_t& payload_bytes)
+              hipEvent_t before_l, bool exact, uint64_t payload_slack, std::vector<uint32_t>& out_len,
+              uint64_t& payload_bytes)
 {
     out_len.assign(tasks.size(), 0);
     if (tasks.empty()) return 0;
     c->coder_restarts = 0;
     c->paths_r = false;
-    c->paths.l_chunk = c->l_chunk == 16 ? 16u : 32u;
+    c->paths.l_chunk = c->knobs.l_chunk;
     c->paths.l_stream = c->st5 ? 1u : 0u;
     std::vector<uint64_t> gb;
     TaskList tl;
@@ -946,7 +825,7 @@ int coder_run(sa_ctx* c, std::vector<CoderTask>& tasks, CoderView& cv, hipStream
         st = c->st5;
     }
     if (before_l) {
-        if (c->host_waits) SA_CHECK(c, hipEventSynchronize(before_l));   // (see host_waits)
+        if (c->knobs.host_waits) SA_CHECK(c, hipEventSynchronize(before_l));   // (see EngineKnobs::host_waits)
         else SA_CHECK(c, hipStreamWaitEvent(st, before_l, 0));
     }
     if (c->timing && ph_l >= 0) ev_begin(c, ph_l, st);
@@ -961,7 +840,7 @@ int coder_run(sa_ctx* c, std::vector<CoderTask>& tasks, CoderView& cv, hipStream
         SA_CHECK(c, d2h(c, ends.data(), c->d_task_ends.p, 4 * tasks.size(), st));
         SA_CHECK(c, d2h(c, perr, c->d_err.p, 16, st));
         std::vector<uint64_t> probe;
-        if (c->rv_probe && c->probe_waves) {
+        if (c->knobs.rv_probe && c->probe_waves) {
             probe.resize(4ull * c->probe_waves);
             SA_CHECK(c, d2h(c, probe.data(), c->d_probe.p, 32ull * c->probe_waves, st));
         }
@@ -971,10 +850,9 @@ int coder_run(sa_ctx* c, std::vector<CoderTask>& tasks, CoderView& cv, hipStream
             c->err = "range coder: pass R timed out waiting for model records (E_CODER)";
             return -1;
         }
-        uint64_t payload = 0, slack = 4096;
-        if (const char* e = std::getenv("SA_PAYLOAD_SLACK")) slack = std::strtoull(e, nullptr, 10);   // (tests)
+        uint64_t payload = 0;
         for (size_t t = 0; t < tasks.size(); t++) {
-            const uint64_t cap = (uint64_t)ends[t] + ends[t] / 64 + slack;
+            const uint64_t cap = (uint64_t)ends[t] + ends[t] / 64 + payload_slack;
             tasks[t].out_cap = (uint32_t)std::min<uint64_t>(cap, tasks[t].out_cap);
             tasks[t].out_base = payload;
             payload = align_up(payload + tasks[t].out_cap, 16);
@@ -1067,120 +945,64 @@ sa_ctx* sa_create(int device)
         else if (!std::strcmp(e, "spin")) (void)hipSetDeviceFlags(hipDeviceScheduleSpin);
         (void)hipGetLastError();   // (hipErrorSetOnActiveProcess when the device is in use already)
     }
-    sa_ctx* c = new sa_ctx();
-    // pass-R placement knobs (k_coder_rv): waves per workgroup, unused LDS per workgroup
-    if (const char* e = std::getenv("SA_CODER_WAVES")) {
-        const int w = std::atoi(e);
-        c->coder_waves = (w == 1 || w == 2) ? (uint32_t)w : 4u;
-    }
-    if (const char* e = std::getenv("SA_CODER_LDS")) c->coder_lds = (uint32_t)std::min(std::max(std::atoi(e), 0), 160 * 1024);
-    if (c->coder_lds > 64 * 1024 &&
-        (hipFuncSetAttribute(reinterpret_cast<const void*>(&k_coder_rv<0>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                             (int)c->coder_lds) != hipSuccess ||
-         hipFuncSetAttribute(reinterpret_cast<const void*>(&k_coder_rv<5>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                             (int)c->coder_lds) != hipSuccess ||
-         hipFuncSetAttribute(reinterpret_cast<const void*>(&k_coder_rv<6>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                             (int)c->coder_lds) != hipSuccess)) {
-        std::fprintf(stderr, "seqarc_amd: cannot reserve %u B of LDS for pass R\n", c->coder_lds);
-        delete c;
-        return nullptr;
-    }
+    std::unique_ptr<sa_ctx> c(new sa_ctx(parse_knobs(env_get)));   // (a failed create: the destructor cleans up)
+    const EngineKnobs& K = c->knobs;
+    if (K.coder_lds > 64 * 1024)   // pass R's unused LDS (k_coder_rv): above what a launch gets by default
+        for (const void* f : {reinterpret_cast<const void*>(&k_coder_rv<0>), reinterpret_cast<const void*>(&k_coder_rv<5>),
+                              reinterpret_cast<const void*>(&k_coder_rv<6>)})
+            if (hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)K.coder_lds) != hipSuccess) {
+                std::fprintf(stderr, "seqarc_amd: cannot reserve %u B of LDS for pass R\n", K.coder_lds);
+                return nullptr;
+            }
     c->device = device;
-    c->timing = c->trace;
     c->n_cu = (uint32_t)prop.multiProcessorCount;
-    for (int i = 0; i < PH_N; i++) c->ev_beg[i] = c->ev_end[i] = nullptr;
     // st carries the critical path (AUX symbols -> QUAL coder chain).  While the
     // long AUX model runs replay (latency-bound, st4: every 4th CU), the SEQ path
     // (throughput, st3: the other CUs) runs beside them without sharing a SIMD.
-    // (SA_LONG_CU_EVERY / SA_LONG_LDS: tuning overrides of the split and of the
-    //  LDS per long-run workgroup, i.e. how many share a CU)
-    const char* ev = std::getenv("SA_LONG_CU_EVERY");
-    const int every = ev ? std::max(1, std::atoi(ev)) : 4;
-    const char* el = std::getenv("SA_LONG_LDS");
-    c->long_lds = el ? (uint32_t)std::atoi(el) : 0u;
-    if (const char* cp = std::getenv("SA_CHAIN_PRIO")) c->chain_prio = std::atoi(cp) != 0;
-    c->md5_prio = c->chain_prio;
-    if (const char* cp = std::getenv("SA_MD5_PRIO")) c->md5_prio = std::atoi(cp) != 0;
-    std::vector<uint32_t> m_long((prop.multiProcessorCount + 31) / 32, 0u), m_seq(m_long.size(), 0u);
-    for (int cu = 0; cu < prop.multiProcessorCount; cu++)
+    const int ncu = prop.multiProcessorCount, every = K.long_cu_every;
+    std::vector<uint32_t> m_long((ncu + 31) / 32, 0u), m_seq(m_long.size(), 0u);
+    for (int cu = 0; cu < ncu; cu++)
         ((cu % every) == 0 || every == 1 ? m_long : m_seq)[cu / 32] |= 1u << (cu % 32);
     if (every == 1) m_seq = m_long;   // (st3: the coder chains; st4: the long model runs)
-    // (A/B, round 5) SA_RV_CUS=n (1..5, with every = 4): pass R and the L passes
-    // (st3) on n of each 8 CUs only, the front (st) on the others -- the scalar
-    // units of the front's CUs free of chain waves (k_coder_rl showed the
-    // fronts 2-3x faster beside a pass R that leaves the scalar units alone)
-    std::vector<uint32_t> m_front;
-    if (const char* rc = std::getenv("SA_RV_CUS")) {
-        const int n = std::atoi(rc);
-        if (every == 4 && n >= 1 && n <= 5) {
-            m_front.assign(m_long.size(), 0u);
-            std::fill(m_seq.begin(), m_seq.end(), 0u);
-            static const int order[6] = {1, 5, 2, 6, 3, 7};   // (the non-long CUs of each 8, spread)
-            for (int cu = 0; cu < prop.multiProcessorCount; cu++) {
-                bool r = false;
-                for (int k = 0; k < n; k++) r |= (cu % 8) == order[k];
-                (r ? m_seq : m_front)[cu / 32] |= 1u << (cu % 32);
-            }
+    std::vector<uint32_t> m_front;   // (see EngineKnobs::rv_cus)
+    if (every == 4 && K.rv_cus >= 1 && K.rv_cus <= 5) {
+        m_front.assign(m_long.size(), 0u);
+        std::fill(m_seq.begin(), m_seq.end(), 0u);
+        static const int order[6] = {1, 5, 2, 6, 3, 7};   // (the non-long CUs of each 8, spread)
+        for (int cu = 0; cu < ncu; cu++) {
+            bool r = false;
+            for (int k = 0; k < K.rv_cus; k++) r |= (cu % 8) == order[k];
+            (r ? m_seq : m_front)[cu / 32] |= 1u << (cu % 32);
         }
     }
-    {
-        uint32_t ncu_long = 0;
-        for (uint32_t w : m_long) ncu_long += (uint32_t)__builtin_popcount(w);
-        c->long_grid = std::max(1u, 6u * ncu_long);
-        if (const char* lg = std::getenv("SA_LONG_GRID")) c->long_grid = (uint32_t)std::max(1, std::atoi(lg));
-    }
+    uint32_t ncu_long = 0;
+    for (uint32_t w : m_long) ncu_long += (uint32_t)__builtin_popcount(w);
+    c->long_grid = K.long_grid_env ? K.long_grid_env : std::max(1u, 6u * ncu_long);
     c->front_masked = !m_front.empty();
-    if ((m_front.empty() ? hipStreamCreateWithFlags(&c->st, hipStreamNonBlocking)
-                         : hipExtStreamCreateWithCUMask(&c->st, (uint32_t)m_front.size(), m_front.data())) != hipSuccess ||
-        hipExtStreamCreateWithCUMask(&c->st2, (uint32_t)m_long.size(), m_long.data()) != hipSuccess ||
-        hipExtStreamCreateWithCUMask(&c->st3, (uint32_t)m_seq.size(), m_seq.data()) != hipSuccess ||
-        hipExtStreamCreateWithCUMask(&c->st4, (uint32_t)m_long.size(), m_long.data()) != hipSuccess ||
-        hipEventCreateWithFlags(&c->ev_seq_done, hipEventDisableTiming) != hipSuccess ||
-        hipEventCreateWithFlags(&c->ev_long_done, hipEventDisableTiming) != hipSuccess ||
-        hipEventCreateWithFlags(&c->ev_prs_zero, hipEventDisableTiming) != hipSuccess ||
-        hipEventCreateWithFlags(&c->ev_fork, hipEventDisableTiming) != hipSuccess ||
-        hipEventCreateWithFlags(&c->ev_fork_seq, hipEventDisableTiming) != hipSuccess ||
-        hipEventCreateWithFlags(&c->ev_md5_done, hipEventDisableTiming) != hipSuccess ||
-        hipEventCreateWithFlags(&c->ev_r[0], hipEventDisableTiming) != hipSuccess ||
-        hipEventCreateWithFlags(&c->ev_r[1], hipEventDisableTiming) != hipSuccess ||
-        hipEventCreateWithFlags(&c->ev_dense, hipEventDisableTiming) != hipSuccess) {
-        delete c;
+    auto masked = [](hipStream_t* s, const std::vector<uint32_t>& m) {   // (no mask: all CUs)
+        return m.empty() ? hipStreamCreateWithFlags(s, hipStreamNonBlocking)
+                         : hipExtStreamCreateWithCUMask(s, (uint32_t)m.size(), m.data());
+    };
+    if (masked(&c->st, m_front) != hipSuccess || masked(&c->st2, m_long) != hipSuccess ||
+        masked(&c->st3, m_seq) != hipSuccess || masked(&c->st4, m_long) != hipSuccess)
         return nullptr;
+    if (K.l_cu_every == 1) {   // (A/B, round 6) the L passes on the front's CUs (all of them without SA_RV_CUS)
+        if (masked(&c->st5, m_front) != hipSuccess) return nullptr;
+    } else if (K.l_cu_every >= 2) {
+        std::vector<uint32_t> m_l(m_long.size(), 0u);
+        for (int cu = 0; cu < ncu; cu++)   // (offset: not the long runs' CUs when n = 4)
+            if (cu % K.l_cu_every == K.l_cu_every / 2) m_l[cu / 32] |= 1u << (cu % 32);
+        if (masked(&c->st5, m_l) != hipSuccess) return nullptr;
     }
-    if (const char* le = std::getenv("SA_L_CU_EVERY")) {
-        const int n = std::atoi(le);
-        if (n == 1) {   // (A/B, round 6) the L passes on the front's CUs (all of them without SA_RV_CUS)
-            if ((m_front.empty() ? hipStreamCreateWithFlags(&c->st5, hipStreamNonBlocking)
-                                 : hipExtStreamCreateWithCUMask(&c->st5, (uint32_t)m_front.size(), m_front.data())) !=
-                    hipSuccess ||
-                hipEventCreateWithFlags(&c->ev_r_done, hipEventDisableTiming) != hipSuccess) {
-                delete c;
-                return nullptr;
-            }
-        } else if (n >= 2) {
-            std::vector<uint32_t> m_l(m_long.size(), 0u);
-            for (int cu = 0; cu < prop.multiProcessorCount; cu++)
-                if (cu % n == n / 2) m_l[cu / 32] |= 1u << (cu % 32);   // (offset: not the long runs' CUs when n = 4)
-            if (hipExtStreamCreateWithCUMask(&c->st5, (uint32_t)m_l.size(), m_l.data()) != hipSuccess ||
-                hipEventCreateWithFlags(&c->ev_r_done, hipEventDisableTiming) != hipSuccess) {
-                delete c;
-                return nullptr;
-            }
-        }
-    }
-    for (int i = 0; i < PH_N; i++) {
-        if (hipEventCreate(&c->ev_beg[i]) != hipSuccess || hipEventCreate(&c->ev_end[i]) != hipSuccess) {
-            delete c;
+    for (const sa_ctx::Ev& ev : c->events()) {
+        if (ev.e == &c->ev_r_done && !c->st5) continue;   // (only the L passes' own stream waits for it)
+        if ((ev.timed ? hipEventCreate(ev.e) : hipEventCreateWithFlags(ev.e, hipEventDisableTiming)) != hipSuccess)
             return nullptr;
-        }
     }
     c->fs = new FrontShare();
     c->fs->refs = 1;
-    if (hipEventCreateWithFlags(&c->fs->ev_free, hipEventDisableTiming) != hipSuccess) {
-        delete c;
-        return nullptr;
-    }
-    return c;
+    if (hipEventCreateWithFlags(&c->fs->ev_free, hipEventDisableTiming) != hipSuccess) return nullptr;
+    return c.release();
 }
 
 sa_ctx* sa_create_shared(int device, sa_ctx* peer)
@@ -1433,25 +1255,52 @@ void align_chain_fail(sa_align_chain* ch);
 
 namespace {
 
-// One encode of a resident batch; exact: the payload arena sized from the
-// streams' real byte counts after L2 (else the 2-bytes-per-symbol bound).
-// al: the reference path (nullptr: no reference).
-// Returns 0, -1, or 2 when a stream outgrew its exact cap.
-int run_input(sa_ctx* c, const sa_input* I, const sa_cfg* cfg, bool exact, const AlignReq* al = nullptr)
+// One batch on its way through run_input's stages: what they share.  The
+// stages return 0, -1 (c->err set), or 2 from the coder (see run_input).
+struct Batch {
+    const sa_input* I;
+    const sa_cfg* cfg;
+    const AlignReq* al;   // the reference path (nullptr: no reference)
+    bool exact;
+    RunKnobs rk;
+    PathPlan pp;          // decided before the first launch (plan_paths)
+    TotalsPlan tp{};      // ... and once the count scan's totals are back (plan_totals)
+    uint32_t nbk = 0, nr = 0;
+    bool early = false;   // the context's first batch: the turn is taken after its own allocations
+    bool trace = false;   // SA_ALN_TRACE on the reference path
+    // the turn on the device's front scratch: RAII, so a stage that returns
+    // early inside the turn releases it
+    std::optional<FrontTurn> turn;
+    BatchView bv{};
+    AlignView alv{};
+    std::vector<uint32_t> aln_tot;
+    std::vector<uint32_t> tot;   // per block the NCOL column sums (k_scan_reads)
+    BatchPlan bp;                // (its tasks' out_base / out_cap: the coder's when exact)
+    uint64_t payload = 0;
+    CoderView cv{};
+    // the sorts' ping-pong tables and where their results are
+    DBuf *skb[2] = {}, *svb[2] = {}, *akb[2] = {}, *avb[2] = {};
+    int seq_sorted = 0, aux_sorted = 0;
+    SortView svs{}, sva{};
+    std::vector<uint32_t> out_len;
+};
+
+// the words of d_err work is taken from (nullptr: the kernel's static path)
+uint32_t* err_word(sa_ctx* c, uint32_t word, bool on) { return on ? c->d_err.as<uint32_t>() + word : nullptr; }
+
+// ---- checks, the plan, BatchView, the reference path, the turn (a warm
+//      context), the MD5 fork ----
+int batch_begin(sa_ctx* c, Batch& B)
 {
-    if (!c) return -1;
-    if (!I || !cfg || I->device != c->device) {
-        c->err = "sa_run_input: no input, no config, or an input of another device";
-        return -1;
-    }
-    const ReserveScope reserve(c->reserve_blocks, I->nblocks);
+    const sa_input* I = B.I;
+    const sa_cfg* cfg = B.cfg;
     SA_CHECK(c, hipSetDevice(c->device));
     c->have_output = false;
     c->paths = sa_paths{};
     c->paths.aux_dense_next = c->aux_dense ? 1u : 0u;
     if (mail_reset(c)) return -1;
     c->blocks = I->blocks;
-    const uint32_t nbk = I->nblocks;
+    const uint32_t nbk = B.nbk = I->nblocks, nr = B.nr = I->nreads;
     if (nbk == 0) {
         c->final_base.clear();
         c->final_len.clear();
@@ -1463,40 +1312,16 @@ int run_input(sa_ctx* c, const sa_input* I, const sa_cfg* cfg, bool exact, const
         return -1;
     }
     const bool lossy = cfg->lossy > 0.0;   // -l R: param+0x1870 / +0x1878
-    const int k = cfg->slevel + 7;
-    const uint32_t ns = 1u << ((2 * k) & 31);
-    const int seq_bits = (2 * k) & 31;   // NS = 1 << seq_bits (x86 shl masks the count)
-    // k <= 14: the SEQ key carries the base in its low two bits and the values
-    // are the stream position, i.e. the index (the emitter writes no values, the
-    // first sort pass computes them); k = 15 fills all 32 key bits (a key could
-    // equal the sort pad) and order 0 has no sort pass, so they keep values
-    // position << 2 | base (SA_SEQ_PACK=0: always)
-    const uint32_t seq_sh = (ns > 1 && seq_bits <= 28 && !c->seq_unpacked) ? 2u : 0u;
-    // contexts of <= 22 bits (Slevel <= 4): one sort pass over the context's low
-    // 8 (9) bits, the high bkt_sb bits replayed per bucket with the models in LDS
-    // (k_replay_seq_bkt); longer contexts: the full sort and k_replay_seq
-    const bool seq_bkt = c->seq_bucket && seq_sh == 2 && bkt_applies(seq_bits);
-    // (SA_BKT_DB: one more digit bit halves the models a replay wave holds in
-    // LDS -- 2^12 contexts in 20 KB instead of 2^13 in 40 KB at 22 bits --
-    // for twice the waves per CU; 10 bits with the inverse-permutation pass only;
-    // plan_bkt refuses a width whose models do not fit the launch's LDS)
-    const BktPlan bkt = plan_bkt(seq_bits, c->bkt_db_env, c->seq_inv);
-    const int bkt_db = bkt.db, bkt_sb = bkt.sb;
-    const int seq_max_db = seq_bkt ? std::max(bkt_db, (int)SORT_MAX_DB) : (int)SORT_MAX_DB;
-    // (the bucket pass sorts by the context's LOW bits: k_replay_seq_bkt)
-    const int seq_lo = (int)seq_sh,
-              seq_hi = ns > 1 ? (int)seq_sh + (seq_bkt ? seq_bits - bkt_sb : seq_bits) : 0;
-    const int aux_bits = cfg->qlevel > 2 ? 21 : 17;
+    B.rk = run_knobs();
+    B.pp = plan_paths(c->knobs, B.rk, PathCfg{cfg->slevel, cfg->qlevel, lossy, cfg->md5 != 0},
+                      BatchShape{nr, I->seq_bytes, nbk, B.al != nullptr, c->aux_dense});
+    c->rv_batch = B.pp.rv_batch;
     hipStream_t st = c->st;
-    const uint32_t nr = I->nreads;
     FrontShare* F = c->fs;
-    c->rv_batch = c->rv_variant == 0 || c->rv_variant == 5 || c->rv_variant == 6
-                      ? c->rv_variant
-                      : (nr && I->seq_bytes / nr > 1000 ? 0 : 6);   // (see rv_variant)
 
     SA_CHECK(c, c->d_blocks.ensure(sizeof(DevBlock) * nbk));
     SA_CHECK(c, h2d(c, c->d_blocks.p, c->blocks.data(), sizeof(DevBlock) * nbk, st));
-    BatchView bv{};
+    BatchView& bv = B.bv;
     bv.blocks = c->d_blocks.as<DevBlock>();
     bv.nblocks = nbk;
     bv.nreads_total = nr;
@@ -1510,20 +1335,18 @@ int run_input(sa_ctx* c, const sa_input* I, const sa_cfg* cfg, bool exact, const
     bv.name_len = I->d_name_len.as<uint16_t>();
     bv.seq_off = I->d_seq_off.as<uint32_t>();
     bv.seq_len = I->d_seq_len.as<uint32_t>();
-    bv.seq_mask = ns - 1;
+    bv.seq_mask = B.pp.ns - 1;
     bv.qlevel = cfg->qlevel;
     bv.bin_mode = cfg->bin_mode ? 1 : 0;
     bv.md5 = cfg->md5 ? 1 : 0;
     // reference path: the reads are aligned (and the batch placed in the
     // align_info chain) before the front is taken: the chain may wait for
     // the batch before this one, which another context runs
-    std::vector<uint32_t> aln_tot;
-    AlignView alv{};
-    if (al && align_front(c, I, bv, *al, aln_tot, alv)) {
-        align_chain_fail(al->chain);
+    if (B.al && align_front(c, I, bv, *B.al, B.aln_tot, B.alv)) {
+        align_chain_fail(B.al->chain);
         return -1;
     }
-    const bool trace = al && std::getenv("SA_ALN_TRACE");
+    B.trace = B.al && B.rk.aln_trace;
     // the front (prep up to the short model runs) holds the device's front
     // scratch.  (The prep before the turn, overlapping another context's
     // front, measured slower: 12.6 vs 13.9 GB/s, round 3 g3i -- the front
@@ -1533,31 +1356,18 @@ int run_input(sa_ctx* c, const sa_input* I, const sa_cfg* cfg, bool exact, const
     // tens of GB takes ~0.3 s, which inside the turn held up every other
     // context (the command line's first batches: 1.4 s of allocations in
     // series, round 4 r4c).  So the first batch preps, plans and allocates
-    // first, then takes its turn.
-    const bool early = !c->front_warm;
-    std::optional<FrontTurn> front_lock;
-    if (!early) front_lock.emplace(F, st);
-    if (trace && !early) fprintf(stderr, "[align] front turn taken\n");
+    // first, then takes its turn (batch_plan_and_buffers).
+    B.early = !c->front_warm;
+    if (!B.early) B.turn.emplace(F, st);
+    if (B.trace && !B.early) fprintf(stderr, "[align] front turn taken\n");
     SA_CHECK(c, c->d_counts.ensure((size_t)std::max<uint32_t>(nr, 1) * NCOL * 4));
     SA_CHECK(c, c->d_dege_maxq.ensure((size_t)std::max<uint32_t>(nr, 1)));
-    uint8_t* dege_maxq = c->prep_wave ? nullptr : c->d_dege_maxq.as<uint8_t>();   // (k_prep_sq: k_emit's serial path)
     SA_CHECK(c, c->d_totals.ensure((size_t)nbk * NCOL * 4));
     SA_CHECK(c, c->d_name_p.ensure((size_t)std::max<uint32_t>(nr, 1) * 2));
     SA_CHECK(c, c->d_name_s.ensure((size_t)std::max<uint32_t>(nr, 1) * 2));
     SA_CHECK(c, c->d_maxlen.ensure((size_t)std::max<uint32_t>(nr, 1) * 2));
-    // error words 0-3; the counters work is taken from: 8 wq_prep, 9 wq_emit (the
-    // front kernels' reads, WaveReads), 10 wq_dege (k_emit_sq's listed reads),
-    // 11 wq_spec (k_rb_spec's chunks)
-    SA_CHECK(c, c->d_err.ensure(64));
-    SA_CHECK(c, hipMemsetAsync(c->d_err.p, 0, 64, st));
-
-    uint32_t* d_err = c->d_err.as<uint32_t>();
-    // the front kernels' dynamic read counters (nullptr: the static grid stride)
-    uint32_t* wq_prep = c->front_static ? nullptr : d_err + 8;
-    uint32_t* wq_emit = c->front_static ? nullptr : d_err + 9;
-    const uint32_t wqc = front_wq_chunk(c, I->seq_bytes, nr);
-    // k_emit_sq's listed reads from a counter (one a take) for long-read batches
-    uint32_t* wq_dege = c->front_static || wqc >= WQ_CHUNK ? nullptr : d_err + 10;
+    SA_CHECK(c, c->d_err.ensure(ERR_BYTES));   // (its words: sa_device.h)
+    SA_CHECK(c, hipMemsetAsync(c->d_err.p, 0, ERR_BYTES, st));
 
     ev_begin(c, PH_TOTAL, st);
     // ---- MD5 of every block's IDs/bases/quals (calcBlockMd5@0x414d90) on st2,
@@ -1569,70 +1379,76 @@ int run_input(sa_ctx* c, const sa_input* I, const sa_cfg* cfg, bool exact, const
         md5t.push_back(Md5Task{I->d_seq.as<uint8_t>() + d.seq_base, d.seq_bytes});
         md5t.push_back(Md5Task{I->d_qual.as<uint8_t>() + d.seq_base, d.seq_bytes});
     }
-    if (cfg->md5) {
+    if (B.pp.md5) {
         SA_CHECK(c, c->d_md5tasks.ensure(sizeof(Md5Task) * md5t.size()));
         SA_CHECK(c, c->d_digests.ensure(16 * md5t.size()));
         SA_CHECK(c, hipEventRecord(c->ev_fork, st));
         SA_CHECK(c, hipStreamWaitEvent(c->st2, c->ev_fork, 0));
         SA_CHECK(c, h2d(c, c->d_md5tasks.p, md5t.data(), sizeof(Md5Task) * md5t.size(), c->st2));
         ev_begin(c, PH_MD5, c->st2);
-        hipLaunchKernelGGL(c->md5_pipe ? k_md5<true> : k_md5<false>, dim3((uint32_t)md5t.size()), dim3(128), 0, c->st2,
+        hipLaunchKernelGGL(B.pp.md5 == 2 ? k_md5<true> : k_md5<false>, dim3((uint32_t)md5t.size()), dim3(128), 0, c->st2,
                            c->d_md5tasks.as<Md5Task>(),
-                           (uint32_t)md5t.size(), c->d_digests.as<uint32_t>(), c->md5_prio);
-        c->paths.md5 = c->md5_pipe ? 2u : 1u;
+                           (uint32_t)md5t.size(), c->d_digests.as<uint32_t>(), c->knobs.md5_prio);
         ev_finish(c, PH_MD5, c->st2);
         SA_CHECK(c, hipGetLastError());
         SA_CHECK(c, hipEventRecord(c->ev_md5_done, c->st2));
     } else {
         SA_CHECK(c, c->d_digests.ensure(16 * md5t.size()));
     }
-    if (!early && F->have_ev) SA_CHECK(c, hipStreamWaitEvent(st, F->ev_free, 0));   // the previous front is done with it
+    if (!B.early && F->have_ev) SA_CHECK(c, hipStreamWaitEvent(st, F->ev_free, 0));   // the previous front is done with it
+    return 0;
+}
+
+// ---- prep, scan, the totals and the error word back ----
+int front_prep(sa_ctx* c, Batch& B)
+{
+    const PathPlan& p = B.pp;
+    hipStream_t st = c->st;
+    const uint32_t nr = B.nr;
+    const BatchView& bv = B.bv;
+    uint32_t* d_err = c->d_err.as<uint32_t>();
+    uint32_t* counts = c->d_counts.as<uint32_t>();
+    uint32_t* wq_prep = err_word(c, ERR_WQ_PREP, p.front_counter);
     ev_begin(c, PH_PREP, st);
-    if (lossy && run_rblock(c, cfg->lossy, I->seq_bytes, bv)) return -1;
-    // thread-per-read kernels: one thread per read (a grid-stride variant with
-    // 8 workgroups per CU measured slower: k_prep 1.2 -> 1.7 ms, k_emit 6.8 -> 9.4)
-    const uint32_t rgrid = (nr + 255) / 256;
-    // SA_PREP_ROW=64: a whole wave per read (round 6; for long reads the ONT
-    // batch's prep+scan measured the same as with 16-lane rows under load, r6l:
-    // 44.2 / 46.4 against 44.9 / 41.4 ms, so 16 stays the default)
-    const bool prep_wide = c->prep_row == 64;
-    c->paths.wg_per_cu = c->wg_per_cu;
-    if (nr) {
-        c->paths.prep = c->prep_fused ? SA_PATH_PREP_FUSED : c->prep_wave ? SA_PATH_PREP_WAVE : prep_wide ? SA_PATH_PREP_ROW64 : SA_PATH_PREP_ROW16;
-        c->paths.front_counter = wq_prep && !c->prep_wave ? 1u : 0u;   // (k_prep_sq: a static stride)
-        // k_prep (names, lengths: lane per read) and k_prep_sq16 (SEQ / QUAL /
-        // N-IUPAC columns: a row per read).  SA_PREP_FUSED=1: k_prep_sq16 takes
-        // the name columns too (row-parallel prefix / suffix) -- measured no
-        // faster under load (prep 38 vs 32 ms, same GB/s, round 3 g3r / g3s);
-        // SA_PREP_WAVE=1: round 2's wave-per-read k_prep_sq
-        if (c->prep_fused) {
-            hipLaunchKernelGGL(wq_prep ? k_prep_sq16<true> : k_prep_sq16<false>, dim3(wave_grid(c, (nr + 3) / 4)),
-                               dim3(256), 0, st, bv, c->d_counts.as<uint32_t>(), d_err, c->d_dege_maxq.as<uint8_t>(),
-                               c->d_name_p.as<int16_t>(), c->d_name_s.as<int16_t>(), wq_prep, wqc);
-        } else {
-            hipLaunchKernelGGL(k_prep, dim3(rgrid), dim3(256), 0, st, bv, c->d_counts.as<uint32_t>(),
-                               c->d_name_p.as<int16_t>(), c->d_name_s.as<int16_t>(), d_err);
-            if (c->prep_wave)
-                hipLaunchKernelGGL(k_prep_sq, dim3(wave_grid(c, nr)), dim3(64 * EMIT_WAVES), 0, st, bv,
-                                   c->d_counts.as<uint32_t>(), d_err);
-            else if (prep_wide)
-                hipLaunchKernelGGL((wq_prep ? k_prep_sq16<true, 64> : k_prep_sq16<false, 64>), dim3(wave_grid(c, nr)),
-                                   dim3(256), 0, st, bv, c->d_counts.as<uint32_t>(), d_err,
-                                   c->d_dege_maxq.as<uint8_t>(), nullptr, nullptr, wq_prep, wqc);
-            else
-                hipLaunchKernelGGL(wq_prep ? k_prep_sq16<true> : k_prep_sq16<false>,
-                                   dim3(wave_grid(c, (nr + 3) / 4)), dim3(256), 0, st, bv, c->d_counts.as<uint32_t>(),
-                                   d_err, c->d_dege_maxq.as<uint8_t>(), nullptr, nullptr, wq_prep, wqc);
-        }
+    if (bv.lossy && run_rblock(c, p, B.cfg->lossy, B.I->seq_bytes, B.bv)) return -1;
+    // k_prep (names, lengths: lane per read -- a grid-stride variant with 8
+    // workgroups per CU measured slower: k_prep 1.2 -> 1.7 ms, k_emit 6.8 -> 9.4)
+    // and k_prep_sq16 (SEQ / QUAL / N-IUPAC columns: a row per read).
+    // SA_PREP_FUSED=1: k_prep_sq16 takes the name columns too (row-parallel
+    // prefix / suffix) -- measured no faster under load (prep 38 vs 32 ms, same
+    // GB/s, round 3 g3r / g3s); SA_PREP_WAVE=1: round 2's wave-per-read k_prep_sq
+    if (p.prep && p.prep != SA_PATH_PREP_FUSED)
+        hipLaunchKernelGGL(k_prep, dim3((nr + 255) / 256), dim3(256), 0, st, bv, counts, c->d_name_p.as<int16_t>(),
+                           c->d_name_s.as<int16_t>(), d_err);
+    switch (p.prep) {
+    case SA_PATH_PREP_FUSED:
+        hipLaunchKernelGGL(wq_prep ? k_prep_sq16<true> : k_prep_sq16<false>, dim3(wave_grid(c, (nr + 3) / 4)),
+                           dim3(256), 0, st, bv, counts, d_err, c->d_dege_maxq.as<uint8_t>(),
+                           c->d_name_p.as<int16_t>(), c->d_name_s.as<int16_t>(), wq_prep, p.wqc);
+        break;
+    case SA_PATH_PREP_WAVE:
+        hipLaunchKernelGGL(k_prep_sq, dim3(wave_grid(c, nr)), dim3(64 * EMIT_WAVES), 0, st, bv, counts, d_err);
+        break;
+    case SA_PATH_PREP_ROW64:
+        hipLaunchKernelGGL((wq_prep ? k_prep_sq16<true, 64> : k_prep_sq16<false, 64>), dim3(wave_grid(c, nr)),
+                           dim3(256), 0, st, bv, counts, d_err, c->d_dege_maxq.as<uint8_t>(), nullptr, nullptr,
+                           wq_prep, p.wqc);
+        break;
+    case SA_PATH_PREP_ROW16:
+        hipLaunchKernelGGL(wq_prep ? k_prep_sq16<true> : k_prep_sq16<false>, dim3(wave_grid(c, (nr + 3) / 4)),
+                           dim3(256), 0, st, bv, counts, d_err, c->d_dege_maxq.as<uint8_t>(), nullptr, nullptr,
+                           wq_prep, p.wqc);
+        break;
+    default: break;   // (a batch without reads)
     }
-    hipLaunchKernelGGL(k_scan_reads, dim3(nbk), dim3(1024), 0, st, bv, c->d_counts.as<uint32_t>(),
-                       c->d_totals.as<uint32_t>(), c->d_maxlen.as<uint16_t>());
+    hipLaunchKernelGGL(k_scan_reads, dim3(B.nbk), dim3(1024), 0, st, bv, counts, c->d_totals.as<uint32_t>(),
+                       c->d_maxlen.as<uint16_t>());
     SA_CHECK(c, hipGetLastError());
     ev_finish(c, PH_PREP, st);
-    std::vector<uint32_t> tot((size_t)nbk * NCOL);
-    uint32_t herr[4];
-    SA_CHECK(c, d2h(c, tot.data(), c->d_totals.p, tot.size() * 4, st));
-    SA_CHECK(c, d2h(c, herr, c->d_err.p, 16, st));
+    B.tot.assign((size_t)B.nbk * NCOL, 0);
+    uint32_t herr[ERR_WORDS];
+    SA_CHECK(c, d2h(c, B.tot.data(), c->d_totals.p, B.tot.size() * 4, st));
+    SA_CHECK(c, d2h(c, herr, c->d_err.p, 4 * ERR_WORDS, st));
     SA_CHECK(c, sync_d2h(c, st));
     if (herr[0]) {
         char buf[128];
@@ -1640,83 +1456,81 @@ int run_input(sa_ctx* c, const sa_input* I, const sa_cfg* cfg, bool exact, const
         c->err = buf;
         return -1;
     }
+    return 0;
+}
 
-    uint64_t n_ch = 0;   // N / IUPAC bases in the batch
-    for (uint32_t b = 0; b < nbk; b++) n_ch += tot[(size_t)b * NCOL + C_CH];
-
-    // ---- layout of the symbol spaces, coder tasks, md5 tasks, outputs ----
-    BatchPlan bp;
-    if (!plan_batch(c->blocks, tot, bp, al ? &aln_tot : nullptr, alv.mis_model)) {
+// ---- layout of the symbol spaces, coder tasks, md5 tasks, outputs; the
+//      context's own buffers; then (inside the turn) the shared front scratch ----
+int batch_plan_and_buffers(sa_ctx* c, Batch& B)
+{
+    hipStream_t st = c->st;
+    FrontShare* F = c->fs;
+    const uint32_t nbk = B.nbk;
+    BatchPlan& bp = B.bp;
+    if (!plan_batch(c->blocks, B.tot, bp, B.al ? &B.aln_tot : nullptr, B.alv.mis_model)) {
         c->err = "block symbol space too large";
         return -1;
     }
     const SortPlan& ps = bp.seq;
     const SortPlan& pa = bp.aux;
-    std::vector<CoderTask> tasks = bp.tasks;
+    const std::vector<CoderTask>& tasks = bp.tasks;
     c->max_stream_syms = c->total_stream_syms = 0;
     for (const CoderTask& tk : tasks) {
         c->max_stream_syms = std::max<uint64_t>(c->max_stream_syms, tk.n);
         c->total_stream_syms += tk.n;
     }
-    std::vector<AsmBlock> asmb = bp.asmb;
+    uint64_t n_ch = 0;   // N / IUPAC bases in the batch
+    for (uint32_t b = 0; b < nbk; b++) n_ch += B.tot[(size_t)b * NCOL + C_CH];
+    const TotalsPlan& t = B.tp = plan_totals(c->knobs, B.rk, B.pp, BatchShape{B.nr, B.I->seq_bytes, nbk, B.al != nullptr, c->aux_dense},
+                                             ps.total, pa.total, n_ch);
+    report_paths(c->paths, c->knobs, B.pp, t, ps.total, pa.total, c->front_masked, c->long_grid);
+    B.payload = bp.payload_bytes;
 
-    // ---- device buffers ----
-    // slack: the replay loops read up to 2 chunks past a run's end, pass R one
-    // 16-record chunk past a stream's last full segment
-    const uint64_t stot = ps.total + KEY_SLACK, atot = pa.total + KEY_SLACK;
-    // AUX sort ping-pong: the sorted keys/values must land in this context's
-    // buffers (the long model runs read them after the front scratch is released)
-    const bool dense = c->aux_dense && aux_bits == (int)AUX_DENSE_BITS && pa.total;
-    const int aux_passes = dense ? 1 : (int)sort_digits(AUX_SYM_BITS, AUX_SYM_BITS + aux_bits).size();
-    const uint64_t max_long = pa.total / LONG_RUN + 1;
-    const uint64_t max_seq_long = ps.total / (SEQ_HALVE_J + 1) + 1;
-    // at most one run per (block, model) and per symbol
-    const uint64_t max_short = std::max<uint64_t>(std::min<uint64_t>(pa.total, (uint64_t)nbk << aux_bits), 1);
-    uint64_t payload = bp.payload_bytes;
-    CoderView cv{};
-    auto ensure_ctx = [&]() -> int {   // this context's own buffers
-        SA_CHECK(c, c->d_auxp_k.ensure(atot * 4));
-        SA_CHECK(c, c->d_auxp_v.ensure(atot * 4));
-        SA_CHECK(c, c->d_prs_seq.ensure(stot * sizeof(PRec)));
-        SA_CHECK(c, c->d_prs_aux.ensure(atot * sizeof(PRec)));
-        SA_CHECK(c, c->d_cum_aux.ensure(atot * 2));
-        SA_CHECK(c, c->d_longs.ensure(max_long * sizeof(LongRun)));
-        SA_CHECK(c, c->d_huge_sorted.ensure((pa.total / HUGE_RUN + 1) * sizeof(LongRun)));
-        SA_CHECK(c, c->d_nlong.ensure(16));   // RunLists counters: short, huge, long, queue
-        SA_CHECK(c, c->d_tasks.ensure(sizeof(CoderTask) * tasks.size()));
-        SA_CHECK(c, c->d_out_len.ensure(4 * tasks.size()));
-        if (!exact) SA_CHECK(c, c->d_payload.ensure(std::max<uint64_t>(payload, 16)));
-        SA_CHECK(c, c->d_asm.ensure(sizeof(AsmBlock) * nbk));
-        SA_CHECK(c, c->d_asm_copies.ensure(4ull * ASM_COPY_WORDS * nbk));
-        SA_CHECK(c, c->d_task_out_base.ensure(8 * tasks.size()));
-        SA_CHECK(c, c->d_final_len.ensure(8 * nbk));
-        return coder_buffers(c, tasks.size(), bp.total_segs, cv);
-    };
-    if (ensure_ctx()) return -1;
-    if (early) {   // (see `early`): now the turn, and the previous front's end on the device
-        front_lock.emplace(F, st);
-        if (trace) fprintf(stderr, "[align] front turn taken\n");
+    // this context's own buffers
+    SA_CHECK(c, c->d_auxp_k.ensure(t.atot * 4));
+    SA_CHECK(c, c->d_auxp_v.ensure(t.atot * 4));
+    SA_CHECK(c, c->d_prs_seq.ensure(t.stot * sizeof(PRec)));
+    SA_CHECK(c, c->d_prs_aux.ensure(t.atot * sizeof(PRec)));
+    SA_CHECK(c, c->d_cum_aux.ensure(t.atot * 2));
+    SA_CHECK(c, c->d_longs.ensure(t.max_long * sizeof(LongRun)));
+    SA_CHECK(c, c->d_huge_sorted.ensure((pa.total / HUGE_RUN + 1) * sizeof(LongRun)));
+    SA_CHECK(c, c->d_nlong.ensure(16));   // RunLists counters: short, huge, long, queue
+    SA_CHECK(c, c->d_tasks.ensure(sizeof(CoderTask) * tasks.size()));
+    SA_CHECK(c, c->d_out_len.ensure(4 * tasks.size()));
+    if (!B.exact) SA_CHECK(c, c->d_payload.ensure(std::max<uint64_t>(B.payload, 16)));
+    SA_CHECK(c, c->d_asm.ensure(sizeof(AsmBlock) * nbk));
+    SA_CHECK(c, c->d_asm_copies.ensure(4ull * ASM_COPY_WORDS * nbk));
+    SA_CHECK(c, c->d_task_out_base.ensure(8 * tasks.size()));
+    SA_CHECK(c, c->d_final_len.ensure(8 * nbk));
+    if (coder_buffers(c, tasks.size(), bp.total_segs, B.cv)) return -1;
+    if (B.early) {   // (see batch_begin): now the turn, and the previous front's end on the device
+        B.turn.emplace(F, st);
+        if (B.trace) fprintf(stderr, "[align] front turn taken\n");
         if (F->have_ev) SA_CHECK(c, hipStreamWaitEvent(st, F->ev_free, 0));
     }
     // the device's front scratch (shared by its contexts: inside the turn)
     for (int i = 0; i < 2; i++) {
-        SA_CHECK(c, F->d_seq_k[i].ensure(stot * 4));
-        SA_CHECK(c, F->d_seq_v[i].ensure(stot * 4));
+        SA_CHECK(c, F->d_seq_k[i].ensure(t.stot * 4));
+        SA_CHECK(c, F->d_seq_v[i].ensure(t.stot * 4));
     }
-    SA_CHECK(c, F->d_auxs_k.ensure(atot * 4));
-    SA_CHECK(c, F->d_auxs_v.ensure(atot * 4));
-    DBuf* akb[2] = {aux_passes % 2 ? &F->d_auxs_k : &c->d_auxp_k, aux_passes % 2 ? &c->d_auxp_k : &F->d_auxs_k};
-    DBuf* avb[2] = {aux_passes % 2 ? &F->d_auxs_v : &c->d_auxp_v, aux_passes % 2 ? &c->d_auxp_v : &F->d_auxs_v};
-    DBuf* skb[2] = {&F->d_seq_k[0], &F->d_seq_k[1]};
-    DBuf* svb[2] = {&F->d_seq_v[0], &F->d_seq_v[1]};
-    int seq_sorted_buf = 0, aux_sorted_buf = 0;
-    SA_CHECK(c, F->d_seq_longs.ensure(max_seq_long * 8));
+    SA_CHECK(c, F->d_auxs_k.ensure(t.atot * 4));
+    SA_CHECK(c, F->d_auxs_v.ensure(t.atot * 4));
+    // AUX sort ping-pong: the sorted keys/values must land in this context's
+    // buffers (the long model runs read them after the front scratch is released)
+    const bool odd = t.aux_passes % 2;
+    B.akb[0] = odd ? &F->d_auxs_k : &c->d_auxp_k;
+    B.akb[1] = odd ? &c->d_auxp_k : &F->d_auxs_k;
+    B.avb[0] = odd ? &F->d_auxs_v : &c->d_auxp_v;
+    B.avb[1] = odd ? &c->d_auxp_v : &F->d_auxs_v;
+    for (int i = 0; i < 2; i++) {
+        B.skb[i] = &F->d_seq_k[i];
+        B.svb[i] = &F->d_seq_v[i];
+    }
+    SA_CHECK(c, F->d_seq_longs.ensure(t.max_seq_long * 8));
     SA_CHECK(c, F->d_nseq_long.ensure(4));
-    SA_CHECK(c, F->d_short_at.ensure(max_short * 8));
-    SA_CHECK(c, F->d_hist_seq.ensure(std::max<uint64_t>(ps.tile_seg.size(), 1) * 4 *
-                                     sort_hist_per_tile(seq_lo, seq_hi, seq_max_db)));
-    SA_CHECK(c, F->d_hist_aux.ensure(std::max<uint64_t>(pa.tile_seg.size(), 1) * 4 *
-                                     sort_hist_per_tile(AUX_SYM_BITS, AUX_SYM_BITS + aux_bits)));
+    SA_CHECK(c, F->d_short_at.ensure(t.max_short * 8));
+    SA_CHECK(c, F->d_hist_seq.ensure(std::max<uint64_t>(ps.tile_seg.size(), 1) * 4 * t.seq_hist_per_tile));
+    SA_CHECK(c, F->d_hist_aux.ensure(std::max<uint64_t>(pa.tile_seg.size(), 1) * 4 * t.aux_hist_per_tile));
     SA_CHECK(c, F->d_segs_seq.ensure(sizeof(SortSeg) * nbk));
     SA_CHECK(c, F->d_segs_aux.ensure(sizeof(SortSeg) * nbk));
     SA_CHECK(c, F->d_tile_seq.ensure(std::max<size_t>(ps.tile_seg.size(), 1) * 4));
@@ -1731,7 +1545,7 @@ int run_input(sa_ctx* c, const sa_input* I, const sa_cfg* cfg, bool exact, const
         SA_CHECK(c, h2d(c, F->d_tile_aux.p, pa.tile_seg.data(), pa.tile_seg.size() * 4, st));
     SA_CHECK(c, h2d(c, c->d_tasks.p, tasks.data(), sizeof(CoderTask) * tasks.size(), st));
 
-
+    CoderView& cv = B.cv;
     cv.tasks = c->d_tasks.as<CoderTask>();
     cv.prs[0] = c->d_prs_seq.as<PRec>();
     cv.prs[1] = c->d_prs_aux.as<PRec>();
@@ -1739,65 +1553,70 @@ int run_input(sa_ctx* c, const sa_input* I, const sa_cfg* cfg, bool exact, const
     cv.cum[1] = c->d_cum_aux.as<uint16_t>();
     cv.out = c->d_payload.as<uint8_t>();
     cv.out_len = c->d_out_len.as<uint32_t>();
-    cv.lprio = c->l_prio;
+    cv.lprio = c->knobs.l_prio;
+    B.svs = SortView{F->d_segs_seq.as<SortSeg>(), F->d_tile_seq.as<uint32_t>(), F->d_hist_seq.as<uint32_t>(),
+                     ps.total, (uint32_t)ps.tile_seg.size(), nbk};
+    B.sva = SortView{F->d_segs_aux.as<SortSeg>(), F->d_tile_aux.as<uint32_t>(), F->d_hist_aux.as<uint32_t>(),
+                     pa.total, (uint32_t)pa.tile_seg.size(), nbk};
+    return 0;
+}
 
-    // ---- emit (main stream) ----
+// ---- emit (main stream), the dense AUX sort's presence pass, the AUX record
+//      array made zero ----
+int front_emit(sa_ctx* c, Batch& B)
+{
+    const PathPlan& p = B.pp;
+    hipStream_t st = c->st;
+    FrontShare* F = c->fs;
+    const uint32_t nbk = B.nbk, nr = B.nr, rgrid = (nr + 255) / 256;
+    const BatchView& bv = B.bv;
+    const SortPlan& ps = B.bp.seq;
+    const SortPlan& pa = B.bp.aux;
+    uint32_t* d_err = c->d_err.as<uint32_t>();
+    uint32_t* counts = c->d_counts.as<uint32_t>();
+    uint32_t* totals = c->d_totals.as<uint32_t>();
+    uint32_t* seq_k = F->d_seq_k[0].as<uint32_t>();
+    uint32_t* seq_v = F->d_seq_v[0].as<uint32_t>();
+    uint32_t* aux_k = B.akb[0]->as<uint32_t>();   // (AUX values: the index, run_sort)
+    uint8_t* dege_maxq = p.dege_maxq ? c->d_dege_maxq.as<uint8_t>() : nullptr;   // (k_prep_sq: k_emit's serial path)
+    uint32_t* wq_emit = err_word(c, ERR_WQ_EMIT, p.front_counter);
     ev_begin(c, PH_EMIT, st);
     {
         const SortView pv_s{F->d_segs_seq.as<SortSeg>(), nullptr, nullptr, ps.total, 0u, nbk};
         const SortView pv_a{F->d_segs_aux.as<SortSeg>(), nullptr, nullptr, pa.total, 0u, nbk};
         const uint32_t pgrid = (uint32_t)(((uint64_t)(nbk + 1) * SORT_TILE + 255) / 256);
-        hipLaunchKernelGGL(k_pad_keys, dim3(pgrid), dim3(256), 0, st, pv_s, F->d_seq_k[0].as<uint32_t>(),
-                           F->d_seq_k[1].as<uint32_t>());
-        hipLaunchKernelGGL(k_pad_keys, dim3(pgrid), dim3(256), 0, st, pv_a, akb[0]->as<uint32_t>(),
-                           akb[1]->as<uint32_t>());
+        hipLaunchKernelGGL(k_pad_keys, dim3(pgrid), dim3(256), 0, st, pv_s, seq_k, F->d_seq_k[1].as<uint32_t>());
+        hipLaunchKernelGGL(k_pad_keys, dim3(pgrid), dim3(256), 0, st, pv_a, aux_k, B.akb[1]->as<uint32_t>());
     }
-    SA_CHECK(c, hipMemsetAsync(c->d_first_sq.p, 0xff, 4 * tasks.size(), st));
-    if (nr) {
-        hipLaunchKernelGGL(k_emit, dim3(rgrid), dim3(256), 0, st, bv, c->d_counts.as<uint32_t>(),
-                           c->d_totals.as<uint32_t>(), c->d_name_p.as<int16_t>(), c->d_name_s.as<int16_t>(),
-                           c->d_maxlen.as<uint16_t>(), F->d_seq_k[0].as<uint32_t>(), F->d_seq_v[0].as<uint32_t>(),
-                           akb[0]->as<uint32_t>(), nullptr, d_err, dege_maxq);   // (AUX values: the index, run_sort)
-        c->paths.emit = c->emit_wave ? SA_PATH_EMIT_WAVE : SA_PATH_EMIT_ROW16;
-        if (c->emit_wave) {   // (SA_EMIT_WAVE=1: round 2's wave-per-read SEQ / QUAL, for A/B)
-            hipLaunchKernelGGL(k_emit_sq, dim3(wave_grid(c, nr)), dim3(64 * EMIT_WAVES), 0, st, bv,
-                               c->d_counts.as<uint32_t>(), F->d_seq_k[0].as<uint32_t>(), F->d_seq_v[0].as<uint32_t>(),
-                               akb[0]->as<uint32_t>(), nullptr, c->d_totals.as<uint32_t>(), dege_maxq, seq_sh,
-                               (uint32_t)(EMIT_SEQ | EMIT_QUAL | EMIT_DEGE), nullptr, nullptr);
-        } else {
-            hipLaunchKernelGGL(seq_sh ? (wq_emit ? k_emit_sq16<2, true> : k_emit_sq16<2, false>)
-                                      : (wq_emit ? k_emit_sq16<0, true> : k_emit_sq16<0, false>),
-                               dim3(wave_grid(c, (nr + 3) / 4)), dim3(256), 0,
-                               st, bv, c->d_counts.as<uint32_t>(), F->d_seq_k[0].as<uint32_t>(),
-                               F->d_seq_v[0].as<uint32_t>(), akb[0]->as<uint32_t>(), nullptr, wq_emit, wqc);
-            if (wq_emit) c->paths.front_counter = 1;
-            if (dege_maxq && n_ch) {   // the N / IUPAC side streams of the reads that have such bases
-                c->paths.dege_list = 1;
-                SA_CHECK(c, c->d_dege_list.ensure(4ull * ((uint64_t)nr + 1)));
-                SA_CHECK(c, hipMemsetAsync(c->d_dege_list.p, 0, 4, st));
-                hipLaunchKernelGGL(k_dege_list, dim3(std::max<uint32_t>(1, std::min<uint32_t>((nr + 255) / 256, c->n_cu * 4))),
-                                   dim3(256), 0, st, bv, c->d_counts.as<uint32_t>(), c->d_totals.as<uint32_t>(),
-                                   c->d_dege_list.as<uint32_t>());
-                hipLaunchKernelGGL(k_emit_sq, dim3(wave_grid(c, nr)), dim3(64 * EMIT_WAVES), 0, st, bv,
-                                   c->d_counts.as<uint32_t>(), F->d_seq_k[0].as<uint32_t>(),
-                                   F->d_seq_v[0].as<uint32_t>(), akb[0]->as<uint32_t>(), nullptr,
-                                   c->d_totals.as<uint32_t>(), dege_maxq, seq_sh, (uint32_t)EMIT_DEGE,
-                                   c->d_dege_list.as<uint32_t>(), wq_dege);
-            }
+    SA_CHECK(c, hipMemsetAsync(c->d_first_sq.p, 0xff, 4 * B.bp.tasks.size(), st));
+    if (p.emit)
+        hipLaunchKernelGGL(k_emit, dim3(rgrid), dim3(256), 0, st, bv, counts, totals, c->d_name_p.as<int16_t>(),
+                           c->d_name_s.as<int16_t>(), c->d_maxlen.as<uint16_t>(), seq_k, seq_v, aux_k, nullptr, d_err,
+                           dege_maxq);
+    if (p.emit == SA_PATH_EMIT_WAVE) {   // (SA_EMIT_WAVE=1: round 2's wave-per-read SEQ / QUAL, for A/B)
+        hipLaunchKernelGGL(k_emit_sq, dim3(wave_grid(c, nr)), dim3(64 * EMIT_WAVES), 0, st, bv, counts, seq_k, seq_v,
+                           aux_k, nullptr, totals, dege_maxq, p.seq_sh,
+                           (uint32_t)(EMIT_SEQ | EMIT_QUAL | EMIT_DEGE), nullptr, nullptr);
+    } else if (p.emit == SA_PATH_EMIT_ROW16) {
+        hipLaunchKernelGGL(p.seq_sh ? (wq_emit ? k_emit_sq16<2, true> : k_emit_sq16<2, false>)
+                                    : (wq_emit ? k_emit_sq16<0, true> : k_emit_sq16<0, false>),
+                           dim3(wave_grid(c, (nr + 3) / 4)), dim3(256), 0, st, bv, counts, seq_k, seq_v, aux_k, nullptr,
+                           wq_emit, p.wqc);
+        if (B.tp.dege_list) {   // the N / IUPAC side streams of the reads that have such bases
+            SA_CHECK(c, c->d_dege_list.ensure(4ull * ((uint64_t)nr + 1)));
+            SA_CHECK(c, hipMemsetAsync(c->d_dege_list.p, 0, 4, st));
+            hipLaunchKernelGGL(k_dege_list, dim3(std::max<uint32_t>(1, std::min<uint32_t>((nr + 255) / 256, c->n_cu * 4))),
+                               dim3(256), 0, st, bv, counts, totals, c->d_dege_list.as<uint32_t>());
+            hipLaunchKernelGGL(k_emit_sq, dim3(wave_grid(c, nr)), dim3(64 * EMIT_WAVES), 0, st, bv, counts, seq_k, seq_v,
+                               aux_k, nullptr, totals, dege_maxq, p.seq_sh, (uint32_t)EMIT_DEGE,
+                               c->d_dege_list.as<uint32_t>(), err_word(c, ERR_WQ_DEGE, p.dege_counter));
         }
-        if (al)   // the alignment streams (AlignInfoProcess[PE], decomposeAlignInfo)
-            hipLaunchKernelGGL(k_align_emit, dim3(rgrid), dim3(256), 0, st, bv, alv, c->d_acounts.as<uint32_t>(),
-                               akb[0]->as<uint32_t>());
     }
+    if (p.emit && B.al)   // the alignment streams (AlignInfoProcess[PE], decomposeAlignInfo)
+        hipLaunchKernelGGL(k_align_emit, dim3(rgrid), dim3(256), 0, st, bv, B.alv, c->d_acounts.as<uint32_t>(), aux_k);
     SA_CHECK(c, hipGetLastError());
     ev_finish(c, PH_EMIT, st);
-    SortView svs{F->d_segs_seq.as<SortSeg>(), F->d_tile_seq.as<uint32_t>(), F->d_hist_seq.as<uint32_t>(),
-                 ps.total, (uint32_t)ps.tile_seg.size(), nbk};
-    SortView sva{F->d_segs_aux.as<SortSeg>(), F->d_tile_aux.as<uint32_t>(), F->d_hist_aux.as<uint32_t>(),
-                 pa.total, (uint32_t)pa.tile_seg.size(), nbk};
-    const SymSink sink_seq{c->d_prs_seq.as<PRec>(), nullptr};   // packed
-    const SymSink sink_aux{c->d_prs_aux.as<PRec>(), c->d_cum_aux.as<uint16_t>()};
-    if (dense) {   // the blocks' model bitmaps and rank tables; the model counts to the host
+    if (B.tp.dense) {   // the blocks' model bitmaps and rank tables; the model counts to the host
         SA_CHECK(c, c->d_aux_bm.ensure(4ull * AUX_DENSE_WORDS * nbk));
         SA_CHECK(c, c->d_aux_tab.ensure(8ull * AUX_DENSE_WORDS * nbk));
         SA_CHECK(c, c->d_aux_nmod.ensure(4ull * nbk));
@@ -1810,21 +1629,14 @@ int run_input(sa_ctx* c, const sa_input* I, const sa_cfg* cfg, bool exact, const
         }
         SA_CHECK(c, hipMemsetAsync(c->d_aux_bm.p, 0, 4ull * AUX_DENSE_WORDS * nbk, st));
         hipLaunchKernelGGL(k_aux_presence, dim3((uint32_t)((pa.tile_seg.size() + PRESENCE_TILES - 1) / PRESENCE_TILES)),
-                           dim3(SORT_THREADS), 0, st, sva,
-                           akb[0]->as<uint32_t>(), c->d_aux_bm.as<uint32_t>());
+                           dim3(SORT_THREADS), 0, st, B.sva, aux_k, c->d_aux_bm.as<uint32_t>());
         hipLaunchKernelGGL(k_aux_dense, dim3(nbk), dim3(256), 0, st, c->d_aux_bm.as<uint32_t>(),
                            c->d_aux_tab.as<uint64_t>(), c->d_aux_nmod.as<uint32_t>());
         SA_CHECK(c, hipGetLastError());
         SA_CHECK(c, hipMemcpyAsync(c->h_aux_nmod, c->d_aux_nmod.p, 4ull * nbk, hipMemcpyDeviceToHost, st));
         SA_CHECK(c, hipEventRecord(c->ev_dense, st));
     }
-
-    // ---- throughput phases on st (each fills the GPU): SEQ sort and BASE_MODEL
-    //      replay, AUX sort and short SIMPLE_MODEL runs.  Then the long SIMPLE_MODEL
-    //      runs (latency-bound, st4: CU set B) and pass R of every coder chain
-    //      (st3: the other CUs) start together: pass R waits per segment for
-    //      records the long runs have not written yet (k_coder_r) ----
-    if (c->prs_zero_p != c->d_prs_aux.p || c->prs_zero_cap < atot * sizeof(PRec)) {
+    if (c->prs_zero_p != c->d_prs_aux.p || c->prs_zero_cap < B.tp.atot * sizeof(PRec)) {
         // (a new buffer, or the last batch did not end normally: zeroed here, all of it)
         SA_CHECK(c, hipMemsetAsync(c->d_prs_aux.p, 0, c->d_prs_aux.cap, st));
     } else if (c->prs_zero_pending) {   // (the previous batch's tail memset: long done by now)
@@ -1833,140 +1645,137 @@ int run_input(sa_ctx* c, const sa_input* I, const sa_cfg* cfg, bool exact, const
     c->prs_zero_p = c->d_prs_aux.p;
     c->prs_zero_cap = 0;   // (until this batch's tail zeroes what it wrote)
     c->prs_zero_pending = false;
+    return 0;
+}
+
+// ---- throughput phases on st (each fills the GPU): the SEQ sort and the
+//      BASE_MODEL replay ----
+int seq_sort_replay(sa_ctx* c, Batch& B)
+{
+    const PathPlan& p = B.pp;
+    hipStream_t st = c->st;
+    FrontShare* F = c->fs;
+    const uint32_t nbk = B.nbk;
+    const SortPlan& ps = B.bp.seq;
+    const SymSink sink_seq{c->d_prs_seq.as<PRec>(), nullptr};   // packed
     ev_begin(c, PH_SORT_SEQ, st);
-    const bool seq_inv = seq_bkt && c->seq_inv;   // (see sa_ctx::seq_inv)
-    if (run_sort(c, st, ps, F->d_segs_seq, F->d_tile_seq, F->d_hist_seq, skb, svb, seq_lo, seq_hi, seq_sorted_buf,
-                 seq_sh != 0, nullptr, seq_inv, seq_max_db))
+    if (run_sort(c, st, ps, F->d_segs_seq, F->d_tile_seq, F->d_hist_seq, B.skb, B.svb, p.seq_lo, p.seq_hi, B.seq_sorted,
+                 p.seq_sh != 0, nullptr, p.seq_inv, p.seq_max_db))
         return -1;
     ev_finish(c, PH_SORT_SEQ, st);
     ev_begin(c, PH_REPLAY_SEQ, st);
-    c->paths.seq_packed = seq_sh == 2 ? 1u : 0u;
-    if (ps.total) c->paths.seq_digits = pack_digits(sort_digits(seq_lo, seq_hi, seq_max_db));
-    if (ps.total && seq_bkt) {
-        const std::vector<int> dg = sort_digits(seq_lo, seq_hi, seq_max_db);   // (one pass: its digit width)
-        if (dg.size() != 1) {
+    const uint32_t* sk = F->d_seq_k[B.seq_sorted].as<uint32_t>();
+    uint32_t* sv = F->d_seq_v[B.seq_sorted].as<uint32_t>();
+    if (ps.total && p.seq_bkt) {
+        if (p.seq_dg.size() != 1) {
             c->err = "internal: the SEQ bucket sort is not one pass";
             return -1;
         }
-        c->paths.seq_replay = SA_PATH_SEQ_BUCKET;
-        c->paths.bkt_inv = seq_inv ? 1u : 0u;
-        c->paths.bkt_lpt = c->bkt_lpt ? 1u : 0u;
-        c->paths.bkt_db = (uint32_t)dg[0];
-        c->paths.bkt_sb = (uint32_t)bkt_sb;
-        const uint32_t bgrid = nbk << dg[0];
+        const uint32_t db = (uint32_t)p.seq_dg[0], sb = (uint32_t)p.bkt.sb, bgrid = nbk << db;
+        const size_t lds = (size_t)5 * ((1u << sb) + 64);
         SA_CHECK(c, F->d_bkt_spare.ensure(256ull * bgrid));
         PRec* spare = F->d_bkt_spare.as<PRec>();
         const uint32_t* border = nullptr;
-        if (c->bkt_lpt) {
-            SA_CHECK(c, F->d_bkt_order.ensure(4ull << dg[0]));
-            hipLaunchKernelGGL(k_bkt_order, dim3(1), dim3(1u << dg[0]), 0, st, svs, 1u << dg[0],
-                               F->d_bkt_order.as<uint32_t>());
+        if (p.bkt_lpt) {
+            SA_CHECK(c, F->d_bkt_order.ensure(4ull << db));
+            hipLaunchKernelGGL(k_bkt_order, dim3(1), dim3(1u << db), 0, st, B.svs, 1u << db, F->d_bkt_order.as<uint32_t>());
             border = F->d_bkt_order.as<uint32_t>();
         }
         uint64_t* bprobe = nullptr;
-        if (c->bkt_probe) {
+        if (c->knobs.bkt_probe) {
             SA_CHECK(c, c->d_bkt_probe.ensure(32ull * bgrid));
             SA_CHECK(c, hipMemsetAsync(c->d_bkt_probe.p, 0, 32ull * bgrid, st));
             bprobe = c->d_bkt_probe.as<uint64_t>();
         }
-        if (seq_inv) {
+        if (p.seq_inv) {
             // records in sorted order into the other value buffer (the bucket
             // pass over implicit values never read it), then gathered through
             // the inverse permutation the pass left in d_seq_v[sorted]
-            PRec* rs = F->d_seq_v[seq_sorted_buf ^ 1].as<PRec>();
-            hipLaunchKernelGGL(k_replay_seq_bkt<true>, dim3(nbk << dg[0]), dim3(64), (size_t)5 * ((1u << bkt_sb) + 64), st, svs,
-                               F->d_seq_k[seq_sorted_buf].as<uint32_t>(), nullptr, SymSink{rs, nullptr},
-                               (uint32_t)dg[0], (uint32_t)bkt_sb, (uint32_t)(seq_sh + dg[0]), spare, bprobe, border);
+            PRec* rs = F->d_seq_v[B.seq_sorted ^ 1].as<PRec>();
+            hipLaunchKernelGGL(k_replay_seq_bkt<true>, dim3(bgrid), dim3(64), lds, st, B.svs, sk, nullptr,
+                               SymSink{rs, nullptr}, db, sb, p.seq_sh + db, spare, bprobe, border);
             hipLaunchKernelGGL(k_seq_unpermute, dim3(8 * (uint32_t)((ps.tile_seg.size() + 7) / 8)),
-                               dim3(SORT_THREADS), 0, st, svs, F->d_seq_v[seq_sorted_buf].as<uint32_t>(), rs,
-                               c->d_prs_seq.as<PRec>());
+                               dim3(SORT_THREADS), 0, st, B.svs, sv, rs, c->d_prs_seq.as<PRec>());
         } else {
-            hipLaunchKernelGGL(k_replay_seq_bkt<false>, dim3(nbk << dg[0]), dim3(64), (size_t)5 * ((1u << bkt_sb) + 64), st, svs,
-                               F->d_seq_k[seq_sorted_buf].as<uint32_t>(), F->d_seq_v[seq_sorted_buf].as<uint32_t>(),
-                               sink_seq, (uint32_t)dg[0], (uint32_t)bkt_sb, (uint32_t)(seq_sh + dg[0]), spare, bprobe, border);
+            hipLaunchKernelGGL(k_replay_seq_bkt<false>, dim3(bgrid), dim3(64), lds, st, B.svs, sk, sv, sink_seq, db, sb,
+                               p.seq_sh + db, spare, bprobe, border);
         }
-        if (bprobe) {   // one line per wave: block, digit (its rank with k_bkt_order), start / end (us, 100 MHz), cycles, steps, shared steps, xcc
-            std::vector<uint64_t> pr(4ull * bgrid);
-            SA_CHECK(c, hipMemcpyAsync(pr.data(), bprobe, 32ull * bgrid, hipMemcpyDeviceToHost, st));
-            SA_CHECK(c, hipStreamSynchronize(st));
-            if (FILE* f = std::fopen(c->bkt_probe, "a")) {
-                for (uint32_t w = 0; w < bgrid; w++) {
-                    const uint64_t* q = &pr[4ull * w];
-                    if (!q[1]) continue;
-                    std::fprintf(f, "%u %u %.2f %.2f %llu %llu %llu %llu\n", border ? w % nbk : w >> dg[0],
-                                 border ? w / nbk : w & ((1u << dg[0]) - 1),   // (k_bkt_order: the digit's rank)
-                                 (double)q[0] / 100.0, (double)q[1] / 100.0, (unsigned long long)q[2],
-                                 (unsigned long long)(q[3] & 0xffffff), (unsigned long long)((q[3] >> 24) & 0xffffff),
-                                 (unsigned long long)(q[3] >> 48));
-                }
-                std::fclose(f);
-            }
-        }
+        if (bprobe && dump_bkt_probe(c, st, bprobe, bgrid, nbk, (int)db, border != nullptr)) return -1;
     } else if (ps.total) {
-        c->paths.seq_replay = SA_PATH_SEQ_FULL;
         SA_CHECK(c, hipMemsetAsync(F->d_nseq_long.p, 0, 4, st));
-        hipLaunchKernelGGL(k_replay_seq, dim3((uint32_t)ps.tile_seg.size()), dim3(SORT_THREADS), 0, st, svs,
-                           F->d_seq_k[seq_sorted_buf].as<uint32_t>(), F->d_seq_v[seq_sorted_buf].as<uint32_t>(),
-                           sink_seq, F->d_seq_longs.as<uint64_t>(), F->d_nseq_long.as<uint32_t>(), seq_sh);
-        hipLaunchKernelGGL(k_replay_seq_long, dim3((uint32_t)std::min<uint64_t>(max_seq_long, 2048)), dim3(128), 0,
-                           st, svs, F->d_seq_k[seq_sorted_buf].as<uint32_t>(),
-                           F->d_seq_v[seq_sorted_buf].as<uint32_t>(), sink_seq, F->d_seq_longs.as<uint64_t>(),
-                           F->d_nseq_long.as<uint32_t>(), d_err, seq_sh);
+        hipLaunchKernelGGL(k_replay_seq, dim3((uint32_t)ps.tile_seg.size()), dim3(SORT_THREADS), 0, st, B.svs, sk, sv,
+                           sink_seq, F->d_seq_longs.as<uint64_t>(), F->d_nseq_long.as<uint32_t>(), p.seq_sh);
+        hipLaunchKernelGGL(k_replay_seq_long, dim3((uint32_t)std::min<uint64_t>(B.tp.max_seq_long, 2048)), dim3(128), 0,
+                           st, B.svs, sk, sv, sink_seq, F->d_seq_longs.as<uint64_t>(), F->d_nseq_long.as<uint32_t>(),
+                           c->d_err.as<uint32_t>(), p.seq_sh);
     }
     SA_CHECK(c, hipGetLastError());
     ev_finish(c, PH_REPLAY_SEQ, st);
+    return 0;
+}
+
+// ---- the AUX sort, the run lists and the short SIMPLE_MODEL runs on st; the
+//      front is released; then the long SIMPLE_MODEL runs (latency-bound, st4:
+//      CU set B), beside which pass R of every coder chain starts (coder_tail) ----
+int aux_sort_runs(sa_ctx* c, Batch& B)
+{
+    const PathPlan& p = B.pp;
+    const TotalsPlan& t = B.tp;
+    hipStream_t st = c->st;
+    FrontShare* F = c->fs;
+    const uint32_t nbk = B.nbk;
+    const SortPlan& pa = B.bp.aux;
+    uint32_t* d_err = c->d_err.as<uint32_t>();
+    const SymSink sink_aux{c->d_prs_aux.as<PRec>(), c->d_cum_aux.as<uint16_t>()};
     ev_begin(c, PH_SORT_AUX, st);
     bool runs_from_hist = false;   // one dense pass: the run lists from the scan (k_runs_dense)
-    if (dense) {
+    if (t.dense) {
         // (the counts were read back right after the emit: the SEQ sort and
         // replay queued above keep the device busy while the host waits here)
         SA_CHECK(c, hipEventSynchronize(c->ev_dense));
         uint32_t dmax = 0;
         for (uint32_t b = 0; b < nbk; b++) dmax = std::max(dmax, c->h_aux_nmod[b]);
-        const int dbits = dmax > 512 ? (int)AUX_DENSE_BITS : 9;
+        const DensePlan dp = plan_dense(dmax, B.rk);
+        runs_from_hist = dp.runs_from_hist;
         c->paths.aux_nmod_max = dmax;
         c->paths.aux_sort = SA_PATH_AUX_DENSE1;
-        c->paths.aux_digits = pack_digits(sort_digits(0, dbits));
-        runs_from_hist = dbits == 9 && !std::getenv("SA_FIND_RUNS");   // (SA_FIND_RUNS=1: k_find_runs, A/B)
-        if (run_sort(c, st, pa, F->d_segs_aux, F->d_tile_aux, F->d_hist_aux, akb, avb, 0, dbits, aux_sorted_buf, true,
+        c->paths.aux_digits = pack_digits(sort_digits(0, dp.dbits));
+        c->paths.aux_runs = runs_from_hist ? SA_PATH_RUNS_DENSE : SA_PATH_RUNS_FIND;
+        if (run_sort(c, st, pa, F->d_segs_aux, F->d_tile_aux, F->d_hist_aux, B.akb, B.avb, 0, dp.dbits, B.aux_sorted, true,
                      c->d_aux_tab.as<uint64_t>()))
             return -1;
-        if (aux_sorted_buf != 1) {   // (two dense passes: the result is in the front scratch)
-            SA_CHECK(c, hipMemcpyAsync(c->d_auxp_k.p, F->d_auxs_k.p, atot * 4, hipMemcpyDeviceToDevice, st));
-            SA_CHECK(c, hipMemcpyAsync(c->d_auxp_v.p, F->d_auxs_v.p, atot * 4, hipMemcpyDeviceToDevice, st));
-            aux_sorted_buf = 1;
+        if (B.aux_sorted != 1) {   // (two dense passes: the result is in the front scratch)
+            SA_CHECK(c, hipMemcpyAsync(c->d_auxp_k.p, F->d_auxs_k.p, t.atot * 4, hipMemcpyDeviceToDevice, st));
+            SA_CHECK(c, hipMemcpyAsync(c->d_auxp_v.p, F->d_auxs_v.p, t.atot * 4, hipMemcpyDeviceToDevice, st));
+            B.aux_sorted = 1;
             c->aux_dense = false;   // (this input has too many models per block for one pass)
             c->paths.aux_sort = SA_PATH_AUX_DENSE2_COPY;
         }
-    } else if (run_sort(c, st, pa, F->d_segs_aux, F->d_tile_aux, F->d_hist_aux, akb, avb, AUX_SYM_BITS,
-                        AUX_SYM_BITS + aux_bits, aux_sorted_buf, true)) {
+    } else if (run_sort(c, st, pa, F->d_segs_aux, F->d_tile_aux, F->d_hist_aux, B.akb, B.avb, AUX_SYM_BITS,
+                        AUX_SYM_BITS + p.aux_bits, B.aux_sorted, true)) {
         return -1;
-    } else if (pa.total) {
-        c->paths.aux_sort = SA_PATH_AUX_RAW;
-        c->paths.aux_digits = pack_digits(sort_digits(AUX_SYM_BITS, AUX_SYM_BITS + aux_bits));
     }
     c->paths.aux_dense_next = c->aux_dense ? 1u : 0u;
     ev_finish(c, PH_SORT_AUX, st);
     ev_begin(c, PH_REPLAY_AUX, st);
-    if (pa.total && akb[aux_sorted_buf] != &c->d_auxp_k) {
+    if (pa.total && B.akb[B.aux_sorted] != &c->d_auxp_k) {
         c->err = "internal: sorted AUX keys not in the context's buffer";
         return -1;
     }
-    const uint32_t* ak = akb[aux_sorted_buf]->as<uint32_t>();
-    const uint32_t* av = avb[aux_sorted_buf]->as<uint32_t>();
+    const uint32_t* ak = B.akb[B.aux_sorted]->as<uint32_t>();   // the sorted AUX keys / values
+    const uint32_t* av = B.avb[B.aux_sorted]->as<uint32_t>();
     uint32_t* ctr = c->d_nlong.as<uint32_t>();
-    const RunLists rl{F->d_short_at.as<uint64_t>(), ctr, c->d_longs.as<LongRun>(), ctr + 1, ctr + 2, max_long, ctr + 3,
+    const RunLists rl{F->d_short_at.as<uint64_t>(), ctr, c->d_longs.as<LongRun>(), ctr + 1, ctr + 2, t.max_long, ctr + 3,
                       c->d_huge_sorted.as<LongRun>()};
     SA_CHECK(c, hipMemsetAsync(ctr, 0, 16, st));
     if (pa.total) {
-        c->paths.aux_runs = runs_from_hist ? SA_PATH_RUNS_DENSE : SA_PATH_RUNS_FIND;
         if (runs_from_hist)
-            hipLaunchKernelGGL(k_runs_dense<9>, dim3((nbk * 512u + 255) / 256), dim3(256), 0, st, sva, ak, rl);
+            hipLaunchKernelGGL(k_runs_dense<9>, dim3((nbk * 512u + 255) / 256), dim3(256), 0, st, B.sva, ak, rl);
         else
             hipLaunchKernelGGL(k_find_runs, dim3((uint32_t)((pa.total / FIND_ITEMS + 255) / 256)), dim3(256), 0, st,
-                               sva, ak, rl);
+                               B.sva, ak, rl);
         hipLaunchKernelGGL(k_sort_huge, dim3(1), dim3(1024), 0, st, rl);
-        hipLaunchKernelGGL(k_replay_aux_short, dim3(SHORT_GRID), dim3(RP_THREADS), 0, st, sva, ak, av, sink_aux, rl,
+        hipLaunchKernelGGL(k_replay_aux_short, dim3(SHORT_GRID), dim3(RP_THREADS), 0, st, B.sva, ak, av, sink_aux, rl,
                            d_err);
     }
     SA_CHECK(c, hipGetLastError());
@@ -1974,42 +1783,54 @@ int run_input(sa_ctx* c, const sa_input* I, const sa_cfg* cfg, bool exact, const
     // the front scratch is free once the kernels enqueued so far on st are done
     SA_CHECK(c, hipEventRecord(F->ev_free, st));
     F->have_ev = true;
-    front_lock->freed = true;
-    front_lock->unlock();
-    hipStream_t st3 = c->st3, st4 = c->st4;
-    c->paths.host_waits = c->host_waits ? 1u : 0u;
-    c->paths.front_masked = c->front_masked ? 1u : 0u;
-    c->paths.long_grid = c->long_grid;
-    if (c->host_waits) SA_CHECK(c, hipEventSynchronize(c->ev_fork_seq));
-    else SA_CHECK(c, hipStreamWaitEvent(st4, c->ev_fork_seq, 0));
-    if (pa.total && !c->test_skip_long)
-        hipLaunchKernelGGL(k_replay_aux_long, dim3(c->long_grid), dim3(128), c->long_lds, st4, rl, ak, av, sink_aux,
-                           d_err, c->chain_prio);
+    B.turn->freed = true;
+    B.turn->unlock();
+    if (c->knobs.host_waits) SA_CHECK(c, hipEventSynchronize(c->ev_fork_seq));
+    else SA_CHECK(c, hipStreamWaitEvent(c->st4, c->ev_fork_seq, 0));
+    if (pa.total && !p.skip_long)
+        hipLaunchKernelGGL(k_replay_aux_long, dim3(c->long_grid), dim3(128), c->knobs.long_lds, c->st4, rl, ak, av, sink_aux,
+                           d_err, c->knobs.chain_prio);
     SA_CHECK(c, hipGetLastError());
-    SA_CHECK(c, hipEventRecord(c->ev_long_done, st4));
-    ev_finish(c, PH_REPLAY_AUX, st4);
+    SA_CHECK(c, hipEventRecord(c->ev_long_done, c->st4));
+    ev_finish(c, PH_REPLAY_AUX, c->st4);
+    return 0;
+}
 
-    // ---- range coders: every chain in one launch on st3, longest first
-    //      (concurrent latency-bound launches land on shared SIMDs); the L passes
-    //      after the long runs are done ----
-    if (!c->host_waits) SA_CHECK(c, hipStreamWaitEvent(st3, c->ev_fork_seq, 0));
-    std::vector<uint32_t> out_len;
-    {
-        // (SA_RV_V6_MAX, see rv_v6_max) the SMEM-fed chain only when few other
-        // contexts' chains are in flight
-        if (c->rv_variant < 0 && c->rv_batch == 6 && F->tails.load() > c->rv_v6_max) c->rv_batch = 5;
-        F->tails++;
-        const int rc = coder_run(c, tasks, cv, st3, PH_CODER_R, PH_CODER_L, c->ev_long_done, exact, out_len, payload);
-        F->tails--;
-        if (rc) return rc;
-    }
-    // the records this batch wrote back to zero, in its tail (after the L passes on st3)
-    SA_CHECK(c, hipMemsetAsync(c->d_prs_aux.p, 0, atot * sizeof(PRec), st3));
+// ---- range coders: every chain in one launch on st3, longest first
+//      (concurrent latency-bound launches land on shared SIMDs): pass R waits
+//      per segment for records the long runs have not written yet (k_coder_r),
+//      the L passes run after the long runs are done; then the AUX records
+//      this batch wrote back to zero ----
+int coder_tail(sa_ctx* c, Batch& B)
+{
+    FrontShare* F = c->fs;
+    hipStream_t st3 = c->st3;
+    if (!c->knobs.host_waits) SA_CHECK(c, hipStreamWaitEvent(st3, c->ev_fork_seq, 0));
+    // (SA_RV_V6_MAX, see EngineKnobs::rv_v6_max) the SMEM-fed chain only when
+    // few other contexts' chains are in flight
+    if (c->knobs.rv_variant < 0 && c->rv_batch == 6 && F->tails.load() > c->knobs.rv_v6_max) c->rv_batch = 5;
+    F->tails++;
+    const int rc = coder_run(c, B.bp.tasks, B.cv, st3, PH_CODER_R, PH_CODER_L, c->ev_long_done, B.exact,
+                             B.rk.payload_slack, B.out_len, B.payload);
+    F->tails--;
+    if (rc) return rc;
+    // (in the batch's tail, after the L passes on st3)
+    SA_CHECK(c, hipMemsetAsync(c->d_prs_aux.p, 0, B.tp.atot * sizeof(PRec), st3));
     SA_CHECK(c, hipEventRecord(c->ev_prs_zero, st3));
     c->prs_zero_cap = c->d_prs_aux.cap;
     c->prs_zero_pending = true;
-    // the final arena from the streams' real sizes: per block its encaps
-    // (<= 32 header bytes each), count / MD5s, and the ID-bin first ID
+    return 0;
+}
+
+// ---- the final arena from the streams' real sizes, the assembly (after MD5),
+//      the lengths and the error word back ----
+int assemble_and_finish(sa_ctx* c, Batch& B)
+{
+    hipStream_t st = c->st;
+    const uint32_t nbk = B.nbk;
+    const std::vector<CoderTask>& tasks = B.bp.tasks;
+    std::vector<AsmBlock>& asmb = B.bp.asmb;
+    // per block its encaps (<= 32 header bytes each), count / MD5s, and the ID-bin first ID
     uint64_t final_bytes = 0;
     std::vector<uint64_t> task_out_base(tasks.size());
     for (size_t t = 0; t < tasks.size(); t++) task_out_base[t] = tasks[t].out_base;
@@ -2017,7 +1838,7 @@ int run_input(sa_ctx* c, const sa_input* I, const sa_cfg* cfg, bool exact, const
     for (uint32_t b = 0; b < nbk; b++) {
         uint64_t blk = 64 + 2 + 0x10000 + 96;
         for (int s = 0; s < NSTREAM; s++)
-            if (asmb[b].task[s] != NO_TASK) blk += out_len[asmb[b].task[s]] + 32;
+            if (asmb[b].task[s] != NO_TASK) blk += B.out_len[asmb[b].task[s]] + 32;
         asmb[b].out_base = final_bytes;
         c->final_base[b] = final_bytes;
         final_bytes = align_up(final_bytes + blk, 16);
@@ -2026,11 +1847,10 @@ int run_input(sa_ctx* c, const sa_input* I, const sa_cfg* cfg, bool exact, const
     SA_CHECK(c, h2d(c, c->d_asm.p, asmb.data(), sizeof(AsmBlock) * nbk, st));
     SA_CHECK(c, h2d(c, c->d_task_out_base.p, task_out_base.data(), 8 * tasks.size(), st));
 
-    // ---- assembly (after MD5) ----
-    if (cfg->md5) SA_CHECK(c, hipStreamWaitEvent(st, c->ev_md5_done, 0));
+    if (B.pp.md5) SA_CHECK(c, hipStreamWaitEvent(st, c->ev_md5_done, 0));
     ev_begin(c, PH_ASM, st);
     AsmView asv{c->d_asm.as<AsmBlock>(), c->d_task_out_base.as<uint64_t>(), c->d_asm_copies.as<uint32_t>()};
-    hipLaunchKernelGGL(k_assemble, dim3((nbk + 63) / 64), dim3(64), 0, st, bv, asv, c->d_out_len.as<uint32_t>(),
+    hipLaunchKernelGGL(k_assemble, dim3((nbk + 63) / 64), dim3(64), 0, st, B.bv, asv, c->d_out_len.as<uint32_t>(),
                        c->d_digests.as<uint32_t>(), c->d_final.as<uint8_t>(), c->d_final_len.as<uint64_t>());
     hipLaunchKernelGGL(k_assemble_copy, dim3(nbk * ASM_SLICES), dim3(256), 0, st, asv, c->d_payload.as<uint8_t>(),
                        c->d_final.as<uint8_t>());
@@ -2039,8 +1859,9 @@ int run_input(sa_ctx* c, const sa_input* I, const sa_cfg* cfg, bool exact, const
     ev_finish(c, PH_TOTAL, st);
 
     c->final_len.assign(nbk, 0);
+    uint32_t herr[ERR_WORDS];
     SA_CHECK(c, d2h(c, c->final_len.data(), c->d_final_len.p, 8ull * nbk, st));
-    SA_CHECK(c, d2h(c, herr, c->d_err.p, 16, st));
+    SA_CHECK(c, d2h(c, herr, c->d_err.p, 4 * ERR_WORDS, st));
     SA_CHECK(c, sync_d2h(c, st));
     if (herr[0]) {
         char buf[128];
@@ -2051,13 +1872,34 @@ int run_input(sa_ctx* c, const sa_input* I, const sa_cfg* cfg, bool exact, const
     if (c->timing) {
         for (int i = 0; i < PH_N; i++) {
             c->ph_ms[i] = 0.f;
-            if (i == PH_MD5 && !cfg->md5) continue;
+            if (i == PH_MD5 && !B.pp.md5) continue;
             (void)hipEventElapsedTime(&c->ph_ms[i], c->ev_beg[i], c->ev_end[i]);
         }
     }
-    if (trace) fprintf(stderr, "[align] batch queued\n");
+    if (B.trace) fprintf(stderr, "[align] batch queued\n");
     c->have_output = true;
     c->front_warm = true;
+    return 0;
+}
+
+// One encode of a resident batch; exact: the payload arena sized from the
+// streams' real byte counts after L2 (else the 2-bytes-per-symbol bound).
+// al: the reference path (nullptr: no reference).
+// Returns 0, -1, or 2 when a stream outgrew its exact cap.
+int run_input(sa_ctx* c, const sa_input* I, const sa_cfg* cfg, bool exact, const AlignReq* al = nullptr)
+{
+    if (!c) return -1;
+    if (!I || !cfg || I->device != c->device) {
+        c->err = "sa_run_input: no input, no config, or an input of another device";
+        return -1;
+    }
+    const ReserveScope reserve(c->reserve_blocks, I->nblocks);
+    Batch B{I, cfg, al, exact};
+    if (const int rc = batch_begin(c, B)) return rc;
+    if (!B.nbk) return 0;   // (an empty batch: done)
+    for (int (*stage)(sa_ctx*, Batch&) : {front_prep, batch_plan_and_buffers, front_emit, seq_sort_replay, aux_sort_runs,
+                                          coder_tail, assemble_and_finish})
+        if (const int rc = stage(c, B)) return rc;
     return 0;
 }
 
@@ -2169,7 +2011,7 @@ int sa_code_records(sa_ctx* c, int nstreams, const uint32_t* lens, const uint16_
     c->paths = sa_paths{};
     c->paths.aux_dense_next = c->aux_dense ? 1u : 0u;
     // (SA_RV_VARIANT holds here too; unset: the last batch's variant, 5 on a fresh context)
-    if (c->rv_variant == 0 || c->rv_variant == 5 || c->rv_variant == 6) c->rv_batch = c->rv_variant;
+    if (c->knobs.rv_variant == 0 || c->knobs.rv_variant == 5 || c->knobs.rv_variant == 6) c->rv_batch = c->knobs.rv_variant;
     SA_CHECK(c, c->d_prs_seq.ensure(prs.size() * sizeof(PRec)));
     SA_CHECK(c, c->d_cum_seq.ensure(cm.size() * 2));
     SA_CHECK(c, c->d_tasks.ensure(sizeof(CoderTask) * std::max<size_t>(tasks.size(), 1)));
@@ -2189,7 +2031,7 @@ int sa_code_records(sa_ctx* c, int nstreams, const uint32_t* lens, const uint16_
     if (coder_buffers(c, tasks.size(), segs, cv)) return -1;
     SA_CHECK(c, hipMemsetAsync(c->d_first_sq.p, 0xff, 4 * std::max<size_t>(tasks.size(), 1), st));
     std::vector<uint32_t> out_len;
-    if (coder_run(c, tasks, cv, st, -1, -1, nullptr, false, out_len, payload)) return -1;
+    if (coder_run(c, tasks, cv, st, -1, -1, nullptr, false, 0, out_len, payload)) return -1;
     std::vector<uint32_t> ol(tasks.size());
     if (!tasks.empty())
         SA_CHECK(c, hipMemcpyAsync(ol.data(), c->d_out_len.p, 4 * tasks.size(), hipMemcpyDeviceToHost, st));
@@ -2253,11 +2095,7 @@ int sa_encode_blocks(sa_ctx* ctx, const sa_block* in, int n, const sa_cfg* cfg, 
     size_t free_b = 0, total_b = 0;
     SA_CHECK(ctx, hipMemGetInfo(&free_b, &total_b));
     const uint64_t budget = (uint64_t)((double)(free_b + ctx->held_bytes()) * 0.85);
-    uint64_t cap_bases = ~0ull;
-    if (const char* e = std::getenv("SA_BATCH_BASES")) {
-        const unsigned long long v = std::strtoull(e, nullptr, 10);
-        if (v > 0) cap_bases = v;
-    }
+    const uint64_t cap_bases = run_knobs().batch_bases;
     int b0 = 0;
     while (b0 < n) {
         int b1 = b0;
@@ -2277,7 +2115,7 @@ int sa_encode_blocks(sa_ctx* ctx, const sa_block* in, int n, const sa_cfg* cfg, 
         if (sa_run(ctx, cfg)) return -1;
         const auto t2 = std::chrono::steady_clock::now();
         if (sa_fetch(ctx, out + b0, b1 - b0)) return -1;
-        if (ctx->trace) {   // SA_TRACE: per sub-batch host-side stage timings
+        if (ctx->knobs.trace) {   // SA_TRACE: per sub-batch host-side stage timings
             const auto t3 = std::chrono::steady_clock::now();
             auto ms = [](auto a, auto b) { return std::chrono::duration<double, std::milli>(b - a).count(); };
             std::string ph;

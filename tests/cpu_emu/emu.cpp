@@ -8,11 +8,16 @@
 // the GPU parity tests (tests/test_gpu_parity.py) check the kernels themselves.
 //
 //   emu [-b block_bytes] [-s slevel] [-q qlevel] [-M] [-r ref.fa [-I insert]] in1.fq [in2.fq]
-//   emu --coder | --bkt-plan
+//   emu --coder | --bkt-plan | --knobs | --path-plan
 //
 // -M: prints each block's number of distinct AUX models (what k_aux_dense
 // counts on the device: the dense AUX sort takes one pass up to 512) and stops.
 // --bkt-plan: prints plan_bkt (sa_plan.h) for every Slevel x SA_BKT_DB x SA_SEQ_INV.
+// --knobs: prints every field parse_knobs / parse_run_knobs (sa_knobs.h) read
+// from this process's environment.
+// --path-plan: with the knobs of this process's environment, prints plan_paths,
+// plan_totals and the sa_paths report_paths fills from them (sa_plan.h) for
+// every Slevel x Qlevel {2, 3} x a short-read and a long-read batch.
 //
 // -r: the reference (HASH index) path: the oracle's index and aligner give
 // every read's alignment under both carried align_info states (what the GPU
@@ -148,6 +153,66 @@ static int bkt_plan_table()
     return 0;
 }
 
+static const char* env_get(const char* n) { return std::getenv(n); }
+
+// Every knob as the engine would read it from this environment: `name value`
+// pairs on one line, checked by tests/test_plan.py.
+static int knobs_table()
+{
+    const EngineKnobs k = parse_knobs(env_get);
+    const RunKnobs r = parse_run_knobs(env_get, parse_sort_min_db(env_get));
+    std::printf("aux_dense %d chain_prio %u md5_prio %u prep_fused %d prep_wave %d emit_wave %d l_chunk %u l_prio %u "
+                "seq_unpacked %d front_static %d wq_chunk_env %u rv_lanes %d seq_bucket %d seq_inv %d bkt_db_env %d "
+                "prep_row %d bkt_lpt %d bkt_probe %d wg_per_cu %u md5_pipe %d host_waits %d coder_waves %u coder_lds %u "
+                "rv_variant %d rv_v6_max %d rv_wait_ticks %u test_skip_long %d rv_short_waves %u trace %d rv_probe %d "
+                "rb_apply_walk %d rb_fix_serial %d rb_spec_wg %u rb_chunk %u long_cu_every %d long_lds %u rv_cus %d "
+                "long_grid_env %u l_cu_every %d payload_slack %llu find_runs %d aln_trace %d batch_bases %llu "
+                "sort_min_db %d\n",
+                k.aux_dense, k.chain_prio, k.md5_prio, k.prep_fused, k.prep_wave, k.emit_wave, k.l_chunk, k.l_prio,
+                k.seq_unpacked, k.front_static, k.wq_chunk_env, k.rv_lanes, k.seq_bucket, k.seq_inv, k.bkt_db_env,
+                k.prep_row, k.bkt_lpt, k.bkt_probe != nullptr, k.wg_per_cu, k.md5_pipe, k.host_waits, k.coder_waves,
+                k.coder_lds, k.rv_variant, k.rv_v6_max, k.rv_wait_ticks, k.test_skip_long, k.rv_short_waves, k.trace,
+                k.rv_probe != nullptr, k.rb_apply_walk, k.rb_fix_serial, k.rb_spec_wg, k.rb_chunk, k.long_cu_every,
+                k.long_lds, k.rv_cus, k.long_grid_env, k.l_cu_every, (unsigned long long)r.payload_slack, r.find_runs,
+                r.aln_trace, (unsigned long long)r.batch_bases, r.sort_min_db);
+    return 0;
+}
+
+// plan_paths / plan_totals / report_paths under this environment's knobs: one
+// line per Slevel x Qlevel x batch shape (16,000 reads of 150 bases; 400 of
+// 2,000), the batch with N / IUPAC bases and both symbol spaces non-empty.
+static int path_plan_table()
+{
+    const EngineKnobs k = parse_knobs(env_get);
+    const RunKnobs rk = parse_run_knobs(env_get, parse_sort_min_db(env_get));
+    static const struct { uint32_t nreads, len; } shapes[] = {{16000, 150}, {400, 2000}};
+    for (int slevel = 0; slevel <= 9; slevel++)
+        for (int qlevel = 2; qlevel <= 3; qlevel++)
+            for (const auto& shp : shapes) {
+                const uint64_t bases = (uint64_t)shp.nreads * shp.len;
+                const BatchShape sh{shp.nreads, bases, 3, false, k.aux_dense};
+                const PathPlan p = plan_paths(k, rk, PathCfg{slevel, qlevel, false, true}, sh);
+                const uint64_t seq_total = bases, aux_total = bases + 40ull * shp.nreads;
+                const TotalsPlan t = plan_totals(k, rk, p, sh, seq_total, aux_total, 7);
+                sa_paths P{};
+                report_paths(P, k, p, t, seq_total, aux_total, false, 384);
+                std::printf("slevel %d qlevel %d len %u seq_bits %d seq_sh %u seq_bkt %d seq_inv %d seq_lo %d seq_hi %d "
+                            "seq_max_db %d aux_bits %d wqc %u dege_counter %d rv_batch %d dense %d aux_passes %d "
+                            "stot %llu atot %llu max_long %llu max_seq_long %llu max_short %llu "
+                            "prep %u front_counter %u wg_per_cu %u emit %u dege_list %u seq_packed %u seq_replay %u "
+                            "bkt_inv %u bkt_lpt %u bkt_db %u bkt_sb %u seq_digits %u aux_sort %u aux_runs %u aux_digits %u "
+                            "host_waits %u md5 %u rblock %u front_masked %u\n",
+                            slevel, qlevel, shp.len, p.seq_bits, p.seq_sh, p.seq_bkt, p.seq_inv, p.seq_lo, p.seq_hi,
+                            p.seq_max_db, p.aux_bits, p.wqc, p.dege_counter, p.rv_batch, t.dense, t.aux_passes,
+                            (unsigned long long)t.stot, (unsigned long long)t.atot, (unsigned long long)t.max_long,
+                            (unsigned long long)t.max_seq_long, (unsigned long long)t.max_short, P.prep,
+                            P.front_counter, P.wg_per_cu, P.emit, P.dege_list, P.seq_packed, P.seq_replay, P.bkt_inv,
+                            P.bkt_lpt, P.bkt_db, P.bkt_sb, P.seq_digits, P.aux_sort, P.aux_runs, P.aux_digits,
+                            P.host_waits, P.md5, P.rblock, P.front_masked);
+            }
+    return 0;
+}
+
 struct HostBlock {
     std::vector<uint8_t> names, seq, qual;
     std::vector<uint16_t> nl;
@@ -179,6 +244,8 @@ int main(int argc, char** argv)
     }
     if (in.size() == 1 && !std::strcmp(in[0], "--coder")) return coder_selftest();
     if (in.size() == 1 && !std::strcmp(in[0], "--bkt-plan")) return bkt_plan_table();
+    if (in.size() == 1 && !std::strcmp(in[0], "--knobs")) return knobs_table();
+    if (in.size() == 1 && !std::strcmp(in[0], "--path-plan")) return path_plan_table();
     if (in.empty()) return 2;
     std::vector<uint8_t> t1 = slurp(in[0]), t2 = in.size() > 1 ? slurp(in[1]) : std::vector<uint8_t>();
     const bool pe = in.size() > 1;

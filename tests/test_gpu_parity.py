@@ -539,6 +539,30 @@ def test_resident_inputs_concurrent_contexts(pe_full):
         assert outs == want[which], (i, rep)
 
 
+def test_rejected_batch_releases_shared_front():
+    """Two contexts sharing one front scratch (sa_create_shared): a batch the
+    device rejects on A (one block of one read with a quality outside the
+    model) must give the front's turn back, or the next front -- B's, then A's
+    own -- waits for it for ever.  Twice: on the fresh A, whose first batch
+    preps before it takes the turn, and on the warm A, which is rejected
+    inside the turn.  Every batch that follows equals the oracle."""
+    bad = fq.parse_se(b"@r\nACGT\n+\nII\x7fI\n")
+    blocks = fq.blocks_from_fastq(synth.edge_cases())
+    cfg = fq.Config()
+    want = _oracle_outs(blocks, cfg)
+    a = fq.Encoder(0)
+    b = fq.Encoder(0, share_with=a)
+    try:
+        for _ in range(2):
+            with pytest.raises(fq.SeqArcError):
+                a.encode([bad], cfg)
+            assert b.encode(blocks, cfg) == want
+            assert a.encode(blocks, cfg) == want
+    finally:
+        b.close()
+        a.close()
+
+
 # ---- sa_stage_text: FASTQ text parsed on the device ------------------------------------------
 
 def _texts(t1, t2=None, bs=fq.BLOCK_SIZE):
