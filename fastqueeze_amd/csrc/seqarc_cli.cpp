@@ -70,6 +70,8 @@
 #include <vector>
 
 #include "../../include/seqarc_amd.h"
+#include "cli_knobs.h"
+#include "cli_plan.h"
 
 namespace {
 
@@ -1043,7 +1045,7 @@ uint64_t count_newlines(const uint8_t* t, uint64_t len)
 // carry copy.  A segment's slot is refilled once the cut has moved past it and
 // every block in it was staged (its text copied to the device) or parsed.
 struct SegReader {
-    static constexpr uint64_t kSlice = 4ull << 20, kChunk = 256ull << 10;
+    static constexpr uint64_t kSlice = cli::kSegSlice, kChunk = 256ull << 10;
     struct Seg {
         uint8_t* p = nullptr;
         uint64_t cap = 0;           // bytes of p
@@ -1067,39 +1069,24 @@ struct SegReader {
     int nf = 1;
     uint64_t S = 0, W = 0;
     bool pinned = false, failed = false, stop = false;
+    int free_threads = 8;   // threads that release the segments (CliKnobs::free_threads)
     std::mutex mu;
     std::condition_variable cv;
     std::vector<std::thread> workers;
     std::atomic<uint64_t> alloc_bytes{0};
     double fill_s = 0;   // fill threads' busy time (under mu)
 
-    // fds: open plain regular files; W: the cut's window
-    bool start(const int* fds, const uint64_t* sizes, int n, uint64_t window, int64_t ahead_bytes, int threads,
-               bool pin, uint64_t batch_blocks = 1)
+    // fds: open plain regular files; the cut's window, a segment's bytes and the
+    // segments per file are the plan's (cli_plan.h: seg_window, seg_bytes, ring_segs)
+    bool start(const int* fds, const uint64_t* sizes, int n, const cli::BatchPlan& plan, int threads, bool pin,
+               int free_thr)
     {
         nf = n;
-        W = window;
+        W = plan.seg_window;
+        S = plan.seg_bytes;
         pinned = pin;
-        uint64_t mx = 0;
-        for (int i = 0; i < n; i++) mx = std::max(mx, sizes[i]);
-        // segments of 512 MiB (a small input: one segment; SA_CLI_SEG_SLICES=n: n slices, for the tests)
-        // (round 5: 256 MiB, SA_CLI_SEG_MIB to change: the ring is unmapped at the
-        // end, ~25 GB/s of page-locked memory, and while device work runs the
-        // unmapping stalls it -- a smaller ring costs less of both, r5x)
-        const char* sm = std::getenv("SA_CLI_SEG_MIB");
-        const uint64_t smax = (uint64_t)(sm ? std::max(4, std::atoi(sm)) : 256) << 20;
-        S = std::max<uint64_t>(kSlice, std::min<uint64_t>(smax, (mx + kSlice - 1) / kSlice * kSlice));
-        if (const char* e = std::getenv("SA_CLI_SEG_SLICES")) S = kSlice * std::max<uint64_t>(1, std::strtoull(e, nullptr, 10));
-        int R = (int)std::max<int64_t>(3, (ahead_bytes + (int64_t)S - 1) / (int64_t)S + 3);
-        // (A/B) SA_CLI_RING_SEGS=n: n segments per file.  The ring is page-locked
-        // once, at ~12 GB/s for the whole process (hipHostRegister does not scale
-        // with threads, profiles/round5_r5a_ingest_probe.txt): a smaller ring
-        // costs less of it before the first pass over it completes
-        if (const char* e = std::getenv("SA_CLI_RING_SEGS")) R = std::max(3, std::atoi(e));
-        // (at least a batch of windows and two segments of slack: the blocks of
-        // a batch keep their segments until the batch is staged; r5i: a ring of
-        // four 512 MiB segments deadlocked a 69-block batch)
-        R = std::max<int>(R, (int)(((uint64_t)batch_blocks * window + S - 1) / S) + 2);
+        free_threads = free_thr;
+        const int R = plan.ring_segs;
         for (int i = 0; i < n; i++) {
             File& F = f[i];
             F.fd = fds[i];
@@ -1123,13 +1110,11 @@ struct SegReader {
         }
         for (auto& t : workers) t.join();
         workers.clear();
-        // (on up to SA_CLI_FREE_THREADS threads, default 8: releasing ~10 GB of
-        // page-locked segments one by one took ~0.47 s past the last encode, r5m)
+        // (on up to free_threads threads, CliKnobs::free_threads)
         std::vector<Seg*> all;
         for (int i = 0; i < nf; i++)
             for (Seg& s : f[i].ring) all.push_back(&s);
-        const char* e = std::getenv("SA_CLI_FREE_THREADS");
-        const size_t nt = std::min<size_t>(all.size(), e ? (size_t)std::max(1, std::atoi(e)) : 8);
+        const size_t nt = std::min<size_t>(all.size(), (size_t)free_threads);
         std::vector<std::thread> th;
         for (size_t t = 1; t < nt; t++)
             th.emplace_back([&, t]() {
@@ -1345,7 +1330,7 @@ struct ParsedPool {
 // kChunk windows each -- one sa_host_alloc per chunk, not per window (the
 // runtime serialises host allocations against the encoder threads' calls).
 struct TextPool {
-    static constexpr size_t kChunk = 16;
+    static constexpr size_t kChunk = cli::kTextChunk;
     std::mutex mu;
     std::vector<Buf<uint8_t>> free;
     std::vector<void*> chunks;
@@ -1416,11 +1401,12 @@ struct TextPool {
 // (and may page-lock) and that is unmapped again once the block is written,
 // every batch.  The pool keeps them for the next batch's blocks; the virtual
 // size is the output bound (~2x the block's symbols), only the written bytes
-// are ever touched.  SA_CLI_OUT_POOL=0: a fresh buffer per block (A/B).
+// are ever touched.  on = false (CliKnobs::out_pool): a fresh buffer per block (A/B).
 struct OutPool {
     std::mutex mu;
     std::vector<Buf<uint8_t>> free;
-    const bool on = !(std::getenv("SA_CLI_OUT_POOL") && std::atoi(std::getenv("SA_CLI_OUT_POOL")) == 0);
+    const bool on;
+    explicit OutPool(bool pool) : on(pool) {}
     void take(Buf<uint8_t>& b, size_t n)
     {
         if (on && !b.cap) {
@@ -1665,18 +1651,12 @@ bool parse_job(Job& j, bool pe, ParsedPool& pool, TextPool& texts, bool keep_tex
     return true;
 }
 
-struct Options {
+struct Options : cli::PlanOpts {   // (PlanOpts, cli_plan.h: the options the batch plan reads)
     const char *f1 = nullptr, *f2 = nullptr, *out = nullptr, *arc = nullptr, *ref = nullptr;
     bool compress = false, decompress = false, index = false, force = false, in_dir = false, share_device = false,
-         verbose = false, host_only = false, host_parse = false, ingest_only = false, ramp = false,
-         release = false, stage_ahead = false, shm = false, maxmis_set = false, ingest_crc = false, gpu_inflate = false;
-    // --read-threads: the plain-file reader's fill threads (SegReader).  16 since
-    // round 6: the whole-node ingest (--ingest-only --devices 8) 34.3 / 35.8
-    // against 18.2 / 28.7 GB/s with 8 (r6s; the reader two or three batches
-    // ahead instead: 21.5-25.4)
-    int read_threads = 16;
+         verbose = false, release = false, shm = false, maxmis_set = false, ingest_crc = false, gpu_inflate = false;
     int writers = 8;        // --writers: the archive writer's copy threads (ArcWriter; 1: write(2) in order)
-    int threads = 0, pipe = 0, device = 0, devices = 1, contexts = 2, batch = 32, block_mib = 50, maxmis = 7;
+    int pipe = 0, device = 0, block_mib = 50, maxmis = 7;
     int insert = 0;
     sa_cfg cfg{3, 2, 1, 0, 0.0};
 };
@@ -1970,230 +1950,128 @@ double g_main_s = 0.0;
     std::_Exit(rc);
 }
 
-int compress(const Options& o)
-{
-    const auto t_start = std::chrono::steady_clock::now();
-    const bool pe = o.f2 && *o.f2;
-    // inflate threads per BGZF input: the -t share (the device parse leaves the host threads free)
-    g_gz_workers = std::max(2, (o.threads > 0 ? o.threads : 16) / (pe ? 2 : 1));
-    g_gpu_inflate_dev = o.gpu_inflate ? o.device : -1;
-    g_gz_verbose = o.verbose;
-    Input in1, in2;
-    struct stat sb;
-    for (const char* f : {o.f1, pe ? o.f2 : nullptr}) {
-        if (f && (stat(f, &sb) != 0 || sb.st_size == 0)) {   // doCheckSetEncodeOpt@0x407fa0
-            fprintf(stderr, "Error:The Src file %s may be not exist or empty!\n", f);
-            return 1;
-        }
-    }
-    if (!in1.open(o.f1) || (pe && !in2.open(o.f2))) {
-        fprintf(stderr, "seqarc_amd: cannot open the input\n");
-        return 1;
-    }
-    std::string outp = o.out;
-    if (o.in_dir && outp.find('/') == std::string::npos) outp = dir_of(o.f1) + outp;
-    const std::string path = outp + ".arc";
-    if (!may_write(path, o.force)) return 1;
+// The -v clocks, in seconds from the start of compress().  add / set_min /
+// set_max are the pipeline's only compare-exchange loops.
+struct Stamps {
+    const std::chrono::steady_clock::time_point t0 = std::chrono::steady_clock::now();
+    double now() const { return std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count(); }
+    static void add(std::atomic<double>& a, double d) { for (double c = a.load(); !a.compare_exchange_weak(c, c + d);) {} }
+    static void set_min(std::atomic<double>& a, double v) { for (double c = a.load(); v < c && !a.compare_exchange_weak(c, v);) {} }
+    static void set_max(std::atomic<double>& a, double v) { for (double c = a.load(); v > c && !a.compare_exchange_weak(c, v);) {} }
+    // the main thread's: contexts ready, encoders started, blocks written, threads joined, archive closed
+    double ctx = 0, enc_start = 0, written = 0, joined = 0, closed = 0;
+    double fill_busy = 0, cut_busy = 0;   // the reader thread's
+    // when the stages first / last did something, and their busy time (any thread)
+    std::atomic<double> read_done{0}, first_enc{1e30}, last_enc{0}, enc_busy{0}, parse_busy{0}, stage_busy{0},
+        seg_freed{0};
+};
 
-    const uint64_t bs = (uint64_t)o.block_mib << 20;   // BlockSize(M), default 50 (param+0x1b78)
-    const int nparse = !o.host_parse && !o.host_only ? 1   // (device parse: block 0 only, for the ID template)
-                       : o.threads > 0 ? o.threads
-                                       : (int)std::max(1u, std::min(16u, std::thread::hardware_concurrency()));
-    // Device parse (default): the reader's text windows are page-locked, the
-    // encoder threads stage them with sa_stage_text (H2D DMA + parse in HBM)
-    // and recycle them at once; only block 0 is parsed here, for the ID
-    // template.  --host-parse / --host-only: -t parser threads build the SoA.
-    const bool dev_parse = !o.host_parse && !o.host_only;
-    ParsedPool pool;   // (declared before the jobs: outlive them)
-    OutPool outpool;
-    // (round 6) the device-parse path sizes each block's output buffer by its
-    // encoded size (sa_fetch_sizes after sa_run) instead of its output bound:
-    // the pool held ~270 buffers of ~180 MB of address space for ~7 MB blocks,
-    // whose teardown was most of the exit (r6z).  SA_CLI_OUT_EXACT=0: the bound (A/B)
-    const bool out_exact = !(std::getenv("SA_CLI_OUT_EXACT") && std::atoi(std::getenv("SA_CLI_OUT_EXACT")) == 0);
-    TextPool texts;
-    texts.pinned = dev_parse && !o.ingest_only;
-    texts.win = (pe ? (size_t)((uint32_t)bs >> 1) : (size_t)bs) + (64u << 10);   // a window + slack for the carry
-    // the windows the reader will hold (two batches ahead of the staging, both
-    // mates), pinned by a thread of their own beside the reader (an input that
-    // is smaller needs fewer)
-    struct Joiner {
-        std::thread t;
-        ~Joiner()
-        {
-            if (t.joinable()) t.join();
-        }
-    } prefill;
-    // plain regular files (not gzip, not a pipe) are read by the segment reader
-    // (SegReader, started below), the others in per-block windows (TextPool)
-    uint64_t fsize[2] = {0, 0};
-    bool seg_plain = o.read_threads > 0 && !in1.is_gz && (!pe || !in2.is_gz) && !std::getenv("SA_CLI_WINDOWS");
-    for (int i = 0; i < (pe ? 2 : 1) && seg_plain; i++) {
-        struct stat st;
-        if (fstat(i ? in2.fd : in1.fd, &st) != 0 || !S_ISREG(st.st_mode)) seg_plain = false;
-        else fsize[i] = (uint64_t)st.st_size;
-    }
-    size_t prefill_chunks = 0;
-    if (texts.pinned && !seg_plain) {
-        size_t wins = (size_t)(pe ? 2 : 1) * (2 * (size_t)std::max(1, o.batch) + 4);
-        uint64_t tot = 0;
-        bool known = true;
-        struct stat st;
-        for (const char* f : {o.f1, pe ? o.f2 : nullptr})
-            if (f) {
-                if (stat(f, &st) == 0 && S_ISREG(st.st_mode) && !in1.is_gz && !in2.is_gz) tot = std::max<uint64_t>(tot, (uint64_t)st.st_size);
-                else known = false;
-            }
-        if (known) wins = std::min(wins, (size_t)(pe ? 2 : 1) * (size_t)(tot / (texts.win - (64u << 10)) + 3));
-        if (const char* e = std::getenv("SA_CLI_PREFILL_WINDOWS")) wins = std::strtoull(e, nullptr, 10);   // (A/B)
-        prefill_chunks = (wins + TextPool::kChunk - 1) / TextPool::kChunk;
-    }
-    // contexts: K per device; every device's contexts share one front scratch
-    std::vector<sa_ctx*> ctxs;
-    std::vector<int> ctx_dev;   // (the device of each context)
+// What the run holds on the devices.  Released by release() or the destructor;
+// leave_to_exit() leaves it all to the process exit (fast_exit).
+struct DeviceSet {
+    std::vector<sa_ctx*> ctxs;        // K per device; every device's contexts share one front scratch
+    std::vector<int> ctx_dev;         // (the device of each context)
+    std::vector<sa_ctx*> stagers;     // --stage-ahead: a staging context per context ...
+    std::vector<sa_input*> sinputs;   // ... and two device inputs
     // reference path: the index on every device in use, one align_info chain
     // through all batches in input order (the reference's -t 1 thread)
-    RefFiles rf;
-    std::map<sa_ctx*, sa_align_cfg> acfg;
     std::vector<sa_hash_index*> indexes;
+    std::vector<sa_align_cfg> acfg;   // (per context)
     sa_align_chain* chain = nullptr;
-    // The plain-file reader starts before the device contexts exist (round 5):
-    // creating five contexts takes ~0.35 s, which the reader's first batch
-    // then overlaps instead of following.  (SA_CLI_EARLY_READ=0: contexts
-    // first, A/B.)  The contexts and the reference index: false with a message.
-    const bool early_read =
-        !(std::getenv("SA_CLI_EARLY_READ") && std::atoi(std::getenv("SA_CLI_EARLY_READ")) == 0) && seg_plain;
-    std::string ctx_err;
-    auto create_contexts = [&]() -> bool {
-        // --ingest-only: the reader and the block cut alone, feeding devices x
-        // contexts consumers that take batches as the device parse would (no device)
-        if (o.host_only || o.ingest_only) ctxs.assign((size_t)o.contexts * (o.ingest_only ? o.devices : 1), nullptr);
-        for (int d = 0; d < o.devices && !o.host_only && !o.ingest_only; d++) {
-            sa_ctx* first = nullptr;
-            for (int k = 0; k < o.contexts; k++) {
-                const int dev = o.device + (o.share_device ? 0 : d);
-                sa_ctx* c = first ? sa_create_shared(dev, first) : sa_create(dev);
-                if (!c) break;
-                if (!first) first = c;
-                ctxs.push_back(c);
-                ctx_dev.push_back(dev);
-            }
-            if (!first) break;
-        }
-        // (started once the contexts exist: pinning beside their creation held
-        // it up, 0.25 -> 0.83 s, round 3 g4j)
-        if (prefill_chunks && !ctxs.empty() && ctxs[0])
-            prefill.t = std::thread([&texts, prefill_chunks]() {
-                for (size_t i = 0; i < prefill_chunks; i++)
-                    if (!texts.grow()) break;
-            });
-        if (o.verbose)
-            for (sa_ctx* c : ctxs)
-                if (c) sa_set_timing(c, 1);
-        if (ctxs.empty()) {
-            ctx_err = "no usable gfx950 device " + std::to_string(o.device);
-            return false;
-        }
-        if (o.ref && !o.host_only && !o.ingest_only) {
-            if (!load_ref(o.ref, false, rf, o.shm, o.verbose)) {
-                ctx_err = std::string("cannot load the reference ") + o.ref;
-                return false;
-            }
-            const double ti = std::chrono::duration<double>(std::chrono::steady_clock::now() - t_start).count();
-            sa_ctx* owner = nullptr;
-            sa_hash_index* ix = nullptr;
-            for (size_t k = 0; k < ctxs.size(); k++) {
-                if (k % (size_t)o.contexts == 0 && !(o.share_device && ix)) {   // the first context of a device
-                    owner = ctxs[k];
-                    ix = rf.have_hash() ? sa_hash_load(owner, rf.hp, rf.hn)
-                                          : sa_hash_build(owner, (const char*)rf.fasta.data(), rf.fasta.size(), 14, 2,
-                                                          1u << 16);
-                    if (!ix) {
-                        ctx_err = std::string("reference index: ") + sa_last_error(owner);
-                        return false;
-                    }
-                    indexes.push_back(ix);
-                }
-                acfg[ctxs[k]] = sa_align_cfg{ix, pe ? 1 : 0, o.maxmis, 1, (uint32_t)o.insert};
-            }
-            chain = sa_align_chain_create(0, 0);   // a fresh encode thread's AlignParam (nmis 0)
-            if (o.verbose)
-                fprintf(stderr, "seqarc_amd: reference %s: index %s in %.3f s\n", o.ref,
-                        rf.have_hash() ? "loaded" : "built",
-                        std::chrono::duration<double>(std::chrono::steady_clock::now() - t_start).count() - ti);
-        }
-        return true;
-    };
-    if (!early_read && !create_contexts()) {
-        fprintf(stderr, "seqarc_amd: %s\n", ctx_err.c_str());
-        return 1;
-    }
-    if (!early_read && !o.host_only && !o.ingest_only && (int64_t)ctxs.size() != (int64_t)o.contexts * o.devices)
-        fprintf(stderr, "seqarc_amd: warning: %zu of %lld encoder contexts created\n", ctxs.size(),
-                (long long)o.contexts * o.devices);
-    int64_t B = std::max(1, o.batch);
-    // (the contexts the options ask for: with early_read they do not exist yet)
-    const int64_t C = early_read ? (int64_t)o.contexts * (o.host_only ? 1 : o.devices) : (int64_t)ctxs.size();
-    // batch k = blocks [bstart(k), bstart(k + 1)).  --ramp: the first batch of
-    // each context ramps up (B (k+1) / (C+1) blocks: the first encode starts
-    // after a fraction of a batch is read, and the contexts' first tails are
-    // staggered); the contexts allocate for B from the start (sa_set_reserve).
-    // Off by default since round 4: a batch's latency is its longest chain's
-    // whatever its size, so the ramp's five small batches cost a round of
-    // throughput (42.8 GB: 5,390 MB/s with it, 6,642 without, r4m).
-    // A plain-file input that fits one round (C batches of B blocks, by its
-    // size) is dealt as C equal batches (round 3 g4g: with the ramp its last
-    // blocks waited for a second round of batch latencies).
-    bool ramp = o.ramp;
-    if (!o.host_only && !o.ingest_only && !in1.is_gz && (!pe || !in2.is_gz)) {
-        uint64_t tot = 0;
-        struct stat st;
-        for (const char* f : {o.f1, pe ? o.f2 : nullptr})
-            if (f && stat(f, &st) == 0 && S_ISREG(st.st_mode)) tot += (uint64_t)st.st_size;
-            else tot = ~0ull >> 1;   // (a pipe: size unknown)
-        const int64_t est = (int64_t)((tot + bs - 1) / bs) + 1;   // blocks (cut at record ends: <= bs each)
-        if (tot < (~0ull >> 2) && est <= C * B) {
-            ramp = false;
-            B = (est + C - 1) / C;
+    bool left = false;   // (a member of the one Pipeline: never copied)
+    ~DeviceSet() { if (!left) release(); }
+    void leave_to_exit() { left = true; }
+    void release()
+    {
+        for (sa_hash_index* ix : indexes) sa_hash_destroy(ix);
+        indexes.clear();
+        if (chain) sa_align_chain_destroy(chain);
+        chain = nullptr;
+        for (sa_input* I : sinputs) sa_input_destroy(I);   // (a null input or context: a creation that failed)
+        sinputs.clear();
+        for (sa_ctx* s : stagers)
+            if (s) sa_destroy(s);
+        stagers.clear();
+        for (sa_ctx*& c : ctxs) {   // (the count stays: report())
+            if (c) sa_destroy(c);
+            c = nullptr;
         }
     }
-    // blocks read but not yet written: C batches encoding and two ahead; with the
-    // streamed staging (below) each context's helper holds one more batch on the
-    // device, its text already back with the reader
-    const bool stream_opt = dev_parse && !o.ingest_only && !o.stage_ahead && std::getenv("SA_CLI_STREAM") &&
-                            std::atoi(std::getenv("SA_CLI_STREAM")) != 0;
-    const size_t max_inflight = (size_t)B * ((size_t)C * (stream_opt ? 2 : 1) + 2);
-    std::vector<int64_t> ramp_start{0};
-    for (int64_t k = 0; ramp && k < C; k++) ramp_start.push_back(ramp_start.back() + std::max<int64_t>(1, B * (k + 1) / (C + 1)));
-    auto bstart = [&](int64_t k) -> int64_t {
-        const int64_t r = (int64_t)ramp_start.size() - 1;
-        return k <= r ? ramp_start[(size_t)k] : ramp_start.back() + (k - r) * B;
-    };
-    auto reserve = [&]() {
-        if (ramp)
-            for (sa_ctx* c : ctxs)
-                if (c) sa_set_reserve(c, (uint32_t)B);
-    };
-    if (!early_read) reserve();
+};
 
+struct Joiner {
+    std::thread t;
+    ~Joiner() { if (t.joinable()) t.join(); }
+};
+
+// One compression run: compress() below is the list of its stages.  The
+// threads are the reader (cuts blocks), the parsers (host parse; block 0's ID
+// template), one encoder per context (and its helper with a feed that stages
+// ahead), the segment ring's releaser and the writer (the calling thread).
+struct Pipeline {
+    // how a batch's blocks become device input, and what the helper thread does meanwhile
+    enum Feed {
+        WHOLE,    // sa_stage_text of the whole batch into the context's own input, in the
+                  // context's cycle (also --host-parse, --host-only and --ingest-only: no helper)
+        AHEAD,    // --stage-ahead: the helper stages the next batch into the alternate sa_input
+                  // with the context's staging context
+        STREAM    // SA_CLI_STREAM=1: sa_text_upload per block as it is cut, the helper uploads
+                  // the next batch into the alternate text arena; sa_text_parse in the cycle
+    };
+    struct Turn {   // a batch in an encoder's hands
+        int64_t k = -1;
+        std::vector<Job*> js;
+        double asked = 0, ready = 0;   // (-v) when the encoder asked for it, when it had it
+    };
+
+    // ---- set by the main thread before the threads that read it start ----
+    const Options& o;
+    const cli::CliKnobs& kn;
+    const bool pe;
+    Stamps st;
+    Input in1, in2;
+    std::string path;
+    cli::PlanIn pin;
+    cli::BatchPlan plan;
+    Feed feed = WHOLE;
+    std::string ctx_err;
+    RefFiles rf;
+    // ---- pools, each with a lock of its own (declared before the jobs: outlive them) ----
+    ParsedPool pool;
+    OutPool outpool;
+    TextPool texts;
+    Joiner prefill;   // pins the windows the reader will hold, beside the reader
+    // ---- guarded by mu (cv signals every change) ----
     std::mutex mu;
     std::condition_variable cv;
-    std::atomic<double> stage_busy{0};
-    std::map<int64_t, std::unique_ptr<Job>> jobs;
-    // -v: when the stages first / last did something (seconds from the start)
-    auto now_s = [&]() { return std::chrono::duration<double>(std::chrono::steady_clock::now() - t_start).count(); };
-    double t_ctx = now_s();   // (early_read: set once the contexts exist)
-    std::atomic<double> t_read_done{0}, t_first_enc{1e30}, t_last_enc{0}, enc_busy{0}, parse_busy{0};
-    double fill_busy = 0, cut_busy = 0;   // (reader thread only)
+    std::map<int64_t, std::unique_ptr<Job>> jobs;   // (a Job's text and output belong to the thread whose turn its state says it is)
     std::deque<int64_t> to_parse;
     int64_t nread = 0, nblocks = -1, written = 0, next_batch = 0, staged = 0;
-    bool failed = false, tmpl_ready = false;
+    bool failed = false, tmpl_ready = false, seg_stop = false;
     std::string err;
-    uint8_t tmpl[512] = {0};
-    sa_cfg cfg = o.cfg;
-    int plus_bare = 1;
     uint64_t total_in = 0;
-    auto fail = [&](const std::string& m) {
+    sa_cfg cfg;   // (bin_mode: written with tmpl_ready, read by the encoders after it)
+    // ---- owned by one thread until the joins ----
+    uint8_t tmpl[512] = {0};   // the parser of block 0
+    int plus_bare = 1;         // the reader
+    // ---- the writer's (the main thread) ----
+    std::vector<sa_arc_block> info;
+    uint64_t total = 0;   // the blocks' bytes
+    uint32_t text_crc = 0;
+    uint8_t hdr[16] = {0};
+    int64_t tl = -1;   // the trailer's bytes
+    int rc = 0;
+    std::unique_ptr<SegReader> segr;
+    std::thread seg_free, reader;
+    std::vector<std::thread> parsers, encoders;
+    ArcWriter aw;
+    DeviceSet dev;
+
+    Pipeline(const Options& opt, const cli::CliKnobs& k)
+        : o(opt), kn(k), pe(opt.f2 && *opt.f2), outpool(k.out_pool), cfg(opt.cfg) {}
+
+    void fail(const std::string& m)
+    {
         {
             std::lock_guard<std::mutex> g(mu);
             if (!failed) err = m;
@@ -2202,140 +2080,279 @@ int compress(const Options& o)
         }
         // contexts waiting on the alignment chain for a batch that will never
         // reach it return instead of waiting forever
-        if (chain) sa_align_chain_fail(chain);
-    };
+        if (dev.chain) sa_align_chain_fail(dev.chain);
+    }
 
-    // plain regular files (not gzip, not a pipe): the segment reader (SegReader)
-    std::unique_ptr<SegReader> segr;
+    // ---- stage: the inputs opened, the output checked, the plan made ----
+    bool open_inputs()
     {
-        if (seg_plain) {
-            const uint64_t win = pe ? (uint64_t)((uint32_t)bs >> 1) : bs;
+        // inflate threads per BGZF input: the -t share (the device parse leaves the host threads free)
+        g_gz_workers = std::max(2, (o.threads > 0 ? o.threads : 16) / (pe ? 2 : 1));
+        g_gpu_inflate_dev = o.gpu_inflate ? o.device : -1;
+        g_gz_verbose = o.verbose;
+        struct stat sb;
+        for (const char* f : {o.f1, pe ? o.f2 : nullptr}) {
+            if (f && (stat(f, &sb) != 0 || sb.st_size == 0)) {   // doCheckSetEncodeOpt@0x407fa0
+                fprintf(stderr, "Error:The Src file %s may be not exist or empty!\n", f);
+                return false;
+            }
+        }
+        if (!in1.open(o.f1) || (pe && !in2.open(o.f2))) {
+            fprintf(stderr, "seqarc_amd: cannot open the input\n");
+            return false;
+        }
+        std::string outp = o.out;
+        if (o.in_dir && outp.find('/') == std::string::npos) outp = dir_of(o.f1) + outp;
+        path = outp + ".arc";
+        if (!may_write(path, o.force)) return false;
+        static_cast<cli::PlanOpts&>(pin) = o;
+        pin.pe = pe;
+        pin.bs = (uint64_t)o.block_mib << 20;   // BlockSize(M), default 50 (param+0x1b78)
+        pin.hw_threads = std::thread::hardware_concurrency();
+        for (int i = 0; i < (pe ? 2 : 1); i++) {
+            const Input& in = i ? in2 : in1;
+            pin.gz[i] = in.is_gz;
+            pin.regular[i] = fstat(in.fd, &sb) == 0 && S_ISREG(sb.st_mode);
+            if (pin.regular[i]) pin.size[i] = (uint64_t)sb.st_size;
+        }
+        // (the contexts the options ask for: they do not exist yet)
+        plan = cli::plan_batches(pin, kn, cli::plan_contexts_asked(pin));
+        texts.pinned = plan.texts_pinned;
+        texts.win = (size_t)plan.text_win;
+        return true;
+    }
+
+    // ---- stage: the contexts (before the reader starts, or with early_read
+    // beside its first batch), the prefill thread, the reference index and the
+    // chain; false with ctx_err ----
+    bool create_contexts()
+    {
+        // --ingest-only: the reader and the block cut alone, feeding devices x
+        // contexts consumers that take batches as the device parse would (no device)
+        if (o.host_only || o.ingest_only) dev.ctxs.assign((size_t)o.contexts * (o.ingest_only ? o.devices : 1), nullptr);
+        for (int d = 0; d < o.devices && !o.host_only && !o.ingest_only; d++) {
+            sa_ctx* first = nullptr;
+            for (int k = 0; k < o.contexts; k++) {
+                const int dv = o.device + (o.share_device ? 0 : d);
+                sa_ctx* c = first ? sa_create_shared(dv, first) : sa_create(dv);
+                if (!c) break;
+                if (!first) first = c;
+                dev.ctxs.push_back(c);
+                dev.ctx_dev.push_back(dv);
+            }
+            if (!first) break;
+        }
+        // (started once the contexts exist: pinning beside their creation held
+        // it up, 0.25 -> 0.83 s, round 3 g4j)
+        if (plan.prefill_chunks && !dev.ctxs.empty() && dev.ctxs[0])
+            prefill.t = std::thread([this, n = plan.prefill_chunks]() {
+                for (size_t i = 0; i < n; i++)
+                    if (!texts.grow()) break;
+            });
+        if (o.verbose)
+            for (sa_ctx* c : dev.ctxs)
+                if (c) sa_set_timing(c, 1);
+        if (dev.ctxs.empty()) {
+            ctx_err = "no usable gfx950 device " + std::to_string(o.device);
+            return false;
+        }
+        if (o.ref && !o.host_only && !o.ingest_only && !load_index()) return false;
+        const int64_t asked = cli::plan_contexts_asked(pin);
+        if ((int64_t)dev.ctxs.size() != asked)
+            fprintf(stderr, "seqarc_amd: warning: %zu of %lld encoder contexts created\n", dev.ctxs.size(),
+                    (long long)asked);
+        // Contexts created before the reader started: the plan again, for the
+        // count created.  (early_read: B, the ring and the in-flight bound were
+        // sized for the count asked for and the reader runs by them already;
+        // fewer contexts only cost pace, hence the warning alone.)
+        if (!plan.early_read) plan = cli::plan_batches(pin, kn, (int64_t)dev.ctxs.size());
+        if (plan.ramp)
+            for (sa_ctx* c : dev.ctxs)
+                if (c) sa_set_reserve(c, (uint32_t)plan.B);
+        st.ctx = st.now();
+        return true;
+    }
+
+    bool load_index()
+    {
+        if (!load_ref(o.ref, false, rf, o.shm, o.verbose)) {
+            ctx_err = std::string("cannot load the reference ") + o.ref;
+            return false;
+        }
+        const double ti = st.now();
+        sa_ctx* owner = nullptr;
+        sa_hash_index* ix = nullptr;
+        dev.acfg.resize(dev.ctxs.size());
+        for (size_t k = 0; k < dev.ctxs.size(); k++) {
+            if (k % (size_t)o.contexts == 0 && !(o.share_device && ix)) {   // the first context of a device
+                owner = dev.ctxs[k];
+                ix = rf.have_hash() ? sa_hash_load(owner, rf.hp, rf.hn)
+                                    : sa_hash_build(owner, (const char*)rf.fasta.data(), rf.fasta.size(), 14, 2, 1u << 16);
+                if (!ix) {
+                    ctx_err = std::string("reference index: ") + sa_last_error(owner);
+                    return false;
+                }
+                dev.indexes.push_back(ix);
+            }
+            dev.acfg[k] = sa_align_cfg{ix, pe ? 1 : 0, o.maxmis, 1, (uint32_t)o.insert};
+        }
+        dev.chain = sa_align_chain_create(0, 0);   // a fresh encode thread's AlignParam (nmis 0)
+        if (o.verbose)
+            fprintf(stderr, "seqarc_amd: reference %s: index %s in %.3f s\n", o.ref, rf.have_hash() ? "loaded" : "built",
+                    st.now() - ti);
+        return true;
+    }
+
+    // ---- stage: the reader (cuts blocks as the input arrives) ----
+    void start_reader()
+    {
+        if (plan.seg_plain) {
             segr.reset(new SegReader());
             const int fds[2] = {in1.fd, in2.fd};
-            // the reader runs at most two batches of blocks ahead of the staging (below)
-            // (one batch of windows ahead of the staging, SA_CLI_AHEAD_BATCHES to change;
-            // two until round 5: the contexts take batches as fast as the reader
-            // cuts them until all are busy, then the device sets the pace)
-            const char* ab = std::getenv("SA_CLI_AHEAD_BATCHES");
-            const int64_t ahead = ab ? std::max(1, std::atoi(ab)) : 1;
-            segr->start(fds, fsize, pe ? 2 : 1, win + (64u << 10), (int64_t)(ahead * B + 2) * (int64_t)win,
-                        o.read_threads, dev_parse, (uint64_t)B);   // (page-locked for the device parse; --ingest-only too)
+            // (page-locked for the device parse; --ingest-only too)
+            segr->start(fds, pin.size, pe ? 2 : 1, plan, o.read_threads, plan.dev_parse, kn.free_threads);
         }
-    }
-    // the segments are released as soon as every block is staged (device parse)
-    std::atomic<double> t_seg_freed{0};
-    std::thread seg_free;
-    bool seg_stop = false;
-    // (SA_CLI_RING_FREE=0, A/B: the ring is left to the process exit)
-    const bool ring_free = !(std::getenv("SA_CLI_RING_FREE") && std::atoi(std::getenv("SA_CLI_RING_FREE")) == 0);
-    if (segr && dev_parse && ring_free)
-        seg_free = std::thread([&]() {
-            {
-                std::unique_lock<std::mutex> lk(mu);
-                cv.wait(lk, [&] { return failed || seg_stop || (nblocks >= 0 && staged >= nblocks); });
-                if (failed || seg_stop) return;
-            }
-            segr->free_all();
-            t_seg_freed = now_s();
-        });
-    // reader: cuts blocks as the input arrives
-    std::thread reader([&]() {
-        if (segr) {   // blocks are views into the segments
-            const uint64_t want = pe ? (uint64_t)((uint32_t)bs >> 1) : bs;
-            std::vector<uint8_t> first;
-            uint64_t o1 = 0, o2 = 0;
-            for (int64_t i = 0;; i++) {
+        // the segments are released as soon as every block is staged (device parse)
+        if (segr && plan.dev_parse && kn.ring_free)
+            seg_free = std::thread([this]() {
                 {
                     std::unique_lock<std::mutex> lk(mu);
-                    cv.wait(lk, [&] {
-                        return failed || ((size_t)(nread - written) < max_inflight && (!dev_parse || nread - staged < 2 * B));
-                    });
-                    if (failed) return;
+                    cv.wait(lk, [&] { return failed || seg_stop || (nblocks >= 0 && staged >= nblocks); });
+                    if (failed || seg_stop) return;
                 }
-                if (o1 >= fsize[0] && (!pe || o2 >= fsize[1])) {   // the input ended on a block boundary
-                    segr->finish();
-                    std::lock_guard<std::mutex> g(mu);
-                    nblocks = i;
-                    cv.notify_all();
-                    return;
-                }
-                const double tf0 = now_s();
-                uint64_t av1 = 0, av2 = 0;
-                int64_t s1 = -1, s2 = -1;
-                const uint8_t* w1 = segr->window(0, o1, av1, s1);
-                const uint8_t* w2 = pe ? segr->window(1, o2, av2, s2) : nullptr;
-                if (!w1 || (pe && !w2)) return fail("read error on the input");
-                const bool eof1 = o1 + av1 >= fsize[0], eof2 = pe && o2 + av2 >= fsize[1];
-                if (i == 0) {
-                    const void* nl = memchr(w1, '\n', (size_t)std::min(av1, want));
-                    first.assign(w1, nl ? (const uint8_t*)nl + 1 : w1 + std::min(av1, want));
-                    plus_bare = pe ? bare_plus(w2, (size_t)std::min(av2, want)) : bare_plus(w1, (size_t)std::min(av1, want));
-                }
-                const double tc0 = now_s();
-                fill_busy += tc0 - tf0;   // (waiting for the fill threads)
-                uint64_t e1 = 0, e2 = 0;
-                if (pe) {
-                    const uint64_t k1 = segr->newlines(0, o1, std::min(av1, want), w1);
-                    const uint64_t k2 = segr->newlines(1, o2, std::min(av2, want), w2);
-                    if (sa_cut_next_pe_nl(w1, av1, eof1, k1, w2, av2, eof2, k2, bs, first.data(), first.size(), &e1,
-                                          &e2) != 0)
-                        return fail("PE block cut failed (mates out of step)");
-                } else {
-                    const int64_t e = sa_cut_next_se(w1, av1, eof1, bs, first.data(), first.size());
-                    if (e < 0) return fail("block cut failed");
-                    e1 = (uint64_t)e;
-                }
-                cut_busy += now_s() - tc0;
-                if (e1 + e2 == 0) return fail("block cut made no progress");
-                std::unique_ptr<Job> j(new Job());
-                auto view = [](Buf<uint8_t>& b, const uint8_t* p, uint64_t n) {
-                    b.d = const_cast<uint8_t*>(p);
-                    b.n = n;
-                    b.cap = 0;   // (not a window: TextPool::put leaves it)
-                    b.external = true;
-                };
-                view(j->t1, w1, e1);
-                if (pe) view(j->t2, w2, e2);
-                j->segr = segr.get();
-                j->seg[0] = s1;
-                j->seg[1] = s2;
-                o1 += e1;
-                o2 += e2;
-                const bool last = o1 >= fsize[0] && (!pe || o2 >= fsize[1]);
-                if (last) {
-                    t_read_done = now_s();
-                    segr->finish();
-                }
-                j->text1 = e1;
-                j->text2 = e2;
-                if (dev_parse && i > 0) j->state = 1;   // (parsed on the device when staged)
-                {
-                    std::lock_guard<std::mutex> g(mu);
-                    total_in += e1 + e2;
-                    jobs[i] = std::move(j);
-                    if (!dev_parse || i == 0) to_parse.push_back(i);
-                    nread = i + 1;
-                    if (last) nblocks = nread;
-                }
-                cv.notify_all();
-                if (last) return;
-            }
+                segr->free_all();
+                st.seg_freed = st.now();
+            });
+        reader = std::thread([this]() {
+            if (segr) read_segments();
+            else read_windows();
+        });
+    }
+
+    // the reader waits for room: blocks in flight, and (device parse) at most
+    // two batches of page-locked text ahead of the staging; false once the run failed
+    bool wait_for_room()
+    {
+        std::unique_lock<std::mutex> lk(mu);
+        cv.wait(lk, [&] {
+            return failed || ((size_t)(nread - written) < plan.max_inflight && (!plan.dev_parse || nread - staged < 2 * plan.B));
+        });
+        return !failed;
+    }
+
+    // block 0: the first line (the cut checks every block's start against it)
+    // and whether the '+' lines are bare
+    void capture_first(std::vector<uint8_t>& first, const uint8_t* p1, size_t n1, const uint8_t* p2, size_t n2)
+    {
+        const void* nl = memchr(p1, '\n', n1);
+        first.assign(p1, nl ? (const uint8_t*)nl + 1 : p1 + n1);
+        plus_bare = pe ? bare_plus(p2, n2) : bare_plus(p1, n1);
+    }
+
+    // the next block's end in each input; nl: the windows' newline counts when
+    // the source has them (the segment reader).  false: fail() was called
+    bool cut(const uint8_t* p1, uint64_t n1, bool eof1, const uint8_t* p2, uint64_t n2, bool eof2,
+             const std::vector<uint8_t>& first, const uint64_t* nl, uint64_t& e1, uint64_t& e2)
+    {
+        const uint64_t bs = pin.bs;
+        e1 = e2 = 0;
+        if (pe) {
+            const int r = nl ? sa_cut_next_pe_nl(p1, n1, eof1, nl[0], p2, n2, eof2, nl[1], bs, first.data(), first.size(), &e1, &e2)
+                             : sa_cut_next_pe(p1, n1, eof1, p2, n2, eof2, bs, first.data(), first.size(), &e1, &e2);
+            if (r != 0) return fail("PE block cut failed (mates out of step)"), false;
+        } else {
+            const int64_t e = sa_cut_next_se(p1, n1, eof1, bs, first.data(), first.size());
+            if (e < 0) return fail("block cut failed"), false;
+            e1 = (uint64_t)e;
         }
+        return true;
+    }
+
+    // block i (e1 / e2 text bytes) to the parsers or the encoders; last: the input ends with it
+    void publish(int64_t i, std::unique_ptr<Job> j, uint64_t e1, uint64_t e2, bool last)
+    {
+        if (last) {
+            st.read_done = st.now();
+            if (segr) segr->finish();
+        }
+        j->text1 = e1;
+        j->text2 = e2;
+        if (plan.dev_parse && i > 0) j->state = 1;   // (parsed on the device when staged)
+        {
+            std::lock_guard<std::mutex> g(mu);
+            total_in += e1 + e2;
+            jobs[i] = std::move(j);
+            if (!plan.dev_parse || i == 0) to_parse.push_back(i);
+            nread = i + 1;
+            if (last) nblocks = nread;
+        }
+        cv.notify_all();
+    }
+
+    void end_input(int64_t i)   // the input ended on a block boundary: i blocks
+    {
+        if (segr) segr->finish();
+        std::lock_guard<std::mutex> g(mu);
+        nblocks = i;
+        cv.notify_all();
+    }
+
+    void read_segments()   // plain regular files: blocks are views into the segments
+    {
+        const uint64_t want = plan.cut_window;
+        std::vector<uint8_t> first;
+        uint64_t o1 = 0, o2 = 0;
+        for (int64_t i = 0;; i++) {
+            if (!wait_for_room()) return;
+            if (o1 >= pin.size[0] && (!pe || o2 >= pin.size[1])) return end_input(i);
+            const double tf0 = st.now();
+            uint64_t av1 = 0, av2 = 0;
+            int64_t s1 = -1, s2 = -1;
+            const uint8_t* w1 = segr->window(0, o1, av1, s1);
+            const uint8_t* w2 = pe ? segr->window(1, o2, av2, s2) : nullptr;
+            if (!w1 || (pe && !w2)) return fail("read error on the input");
+            const bool eof1 = o1 + av1 >= pin.size[0], eof2 = pe && o2 + av2 >= pin.size[1];
+            if (i == 0) capture_first(first, w1, (size_t)std::min(av1, want), w2, (size_t)std::min(av2, want));
+            const double tc0 = st.now();
+            st.fill_busy += tc0 - tf0;   // (waiting for the fill threads)
+            uint64_t e1 = 0, e2 = 0, nl[2] = {0, 0};
+            if (pe) {
+                nl[0] = segr->newlines(0, o1, std::min(av1, want), w1);
+                nl[1] = segr->newlines(1, o2, std::min(av2, want), w2);
+            }
+            if (!cut(w1, av1, eof1, w2, av2, eof2, first, nl, e1, e2)) return;
+            st.cut_busy += st.now() - tc0;
+            if (e1 + e2 == 0) return fail("block cut made no progress");
+            std::unique_ptr<Job> j(new Job());
+            auto view = [](Buf<uint8_t>& b, const uint8_t* p, uint64_t n) {
+                b.d = const_cast<uint8_t*>(p);
+                b.n = n;
+                b.cap = 0;   // (not a window: TextPool::put leaves it)
+                b.external = true;
+            };
+            view(j->t1, w1, e1);
+            if (pe) view(j->t2, w2, e2);
+            j->segr = segr.get();
+            j->seg[0] = s1;
+            j->seg[1] = s2;
+            o1 += e1;
+            o2 += e2;
+            const bool last = o1 >= pin.size[0] && (!pe || o2 >= pin.size[1]);
+            publish(i, std::move(j), e1, e2, last);
+            if (last) return;
+        }
+    }
+
+    void read_windows()   // gzip inputs, pipes, --read-threads 0: per-block windows, the rest carried over
+    {
         Buf<uint8_t> b1 = texts.get(), b2 = texts.get();
         std::vector<uint8_t> first;
-        const uint64_t want = pe ? (uint64_t)((uint32_t)bs >> 1) : bs;
+        const uint64_t want = plan.cut_window;
         for (int64_t i = 0;; i++) {
-            {
-                std::unique_lock<std::mutex> lk(mu);
-                // device parse: at most two batches of page-locked text ahead of the staging
-                cv.wait(lk, [&] {
-                    return failed || ((size_t)(nread - written) < max_inflight && (!dev_parse || nread - staged < 2 * B));
-                });
-                if (failed) return;
-            }
+            if (!wait_for_room()) return;
             b1.reserve(want);
             if (pe) b2.reserve(want);
-            const double tf0 = now_s();
+            const double tf0 = st.now();
             {   // the two mate files are read concurrently
                 std::future<bool> r2;
                 if (pe && b2.size() < want && !in2.eof)
@@ -2345,31 +2362,13 @@ int compress(const Options& o)
                 if (!ok1) return fail("read error on input 1");
                 if (!ok2) return fail("read error on input 2");
             }
-            if (b1.empty() && (!pe || b2.empty())) {   // the input ended on a block boundary
-                std::lock_guard<std::mutex> g(mu);
-                nblocks = i;
-                cv.notify_all();
-                return;
-            }
-            if (i == 0) {
-                const void* nl = memchr(b1.data(), '\n', b1.size());
-                const uint8_t* f0 = b1.data();
-                first.assign(f0, nl ? (const uint8_t*)nl + 1 : f0 + b1.size());
-                plus_bare = pe ? bare_plus(b2.data(), b2.size()) : bare_plus(b1.data(), b1.size());
-            }
-            const double tc0 = now_s();
-            fill_busy += tc0 - tf0;
+            if (b1.empty() && (!pe || b2.empty())) return end_input(i);
+            if (i == 0) capture_first(first, b1.data(), b1.size(), b2.data(), b2.size());
+            const double tc0 = st.now();
+            st.fill_busy += tc0 - tf0;
             uint64_t e1 = 0, e2 = 0;
-            if (pe) {
-                if (sa_cut_next_pe(b1.data(), b1.size(), in1.eof, b2.data(), b2.size(), in2.eof, bs, first.data(),
-                                   first.size(), &e1, &e2) != 0)
-                    return fail("PE block cut failed (mates out of step)");
-            } else {
-                const int64_t e = sa_cut_next_se(b1.data(), b1.size(), in1.eof, bs, first.data(), first.size());
-                if (e < 0) return fail("block cut failed");
-                e1 = (uint64_t)e;
-            }
-            cut_busy += now_s() - tc0;
+            if (!cut(b1.data(), b1.size(), in1.eof, b2.data(), b2.size(), in2.eof, first, nullptr, e1, e2)) return;
+            st.cut_busy += st.now() - tc0;
             std::unique_ptr<Job> j(new Job());
             auto hand_over = [&](Buf<uint8_t>& b, Buf<uint8_t>& to, uint64_t e) {
                 Buf<uint8_t> carry = texts.get();   // the bytes after the cut start the next window
@@ -2383,263 +2382,160 @@ int compress(const Options& o)
             hand_over(b1, j->t1, e1);
             if (pe) hand_over(b2, j->t2, e2);
             const bool last = b1.empty() && b2.empty() && in1.eof && (!pe || in2.eof);
-            if (last) t_read_done = now_s();
-            j->text1 = e1;
-            j->text2 = e2;
-            if (dev_parse && i > 0) j->state = 1;   // (parsed on the device when staged)
-            {
-                std::lock_guard<std::mutex> g(mu);
-                total_in += e1 + e2;
-                jobs[i] = std::move(j);
-                if (!dev_parse || i == 0) to_parse.push_back(i);
-                nread = i + 1;
-                if (last) nblocks = nread;
-            }
-            cv.notify_all();
+            publish(i, std::move(j), e1, e2, last);
             if (last) return;
         }
-    });
+    }
 
-    // parsers
-    std::vector<std::thread> parsers;
-    for (int t = 0; t < nparse; t++)
-        parsers.emplace_back([&]() {
-            for (;;) {
-                int64_t i;
-                Job* j;
-                {
-                    std::unique_lock<std::mutex> lk(mu);
-                    cv.wait(lk, [&] { return failed || !to_parse.empty() || nblocks >= 0; });
-                    if (failed || (to_parse.empty() && nblocks >= 0)) return;
-                    i = to_parse.front();
-                    to_parse.pop_front();
-                    j = jobs[i].get();
-                }
-                const double tp = now_s();
-                if (!parse_job(*j, pe, pool, texts, dev_parse)) return fail("parse failed");
-                {
-                    double cur = parse_busy.load();
-                    while (!parse_busy.compare_exchange_weak(cur, cur + now_s() - tp)) {}
-                }
-                if (i == 0) {   // the ID template of the first block
-                    const sa_block fb = j->p->view();
-                    if (sa_analyze_ids(&fb, pe ? 0 : 1, tmpl) != 0) return fail("ID analysis failed");
-                }
-                if (dev_parse) pool.put(std::move(j->p));   // (only the template needed it)
-                {
-                    std::lock_guard<std::mutex> g(mu);
-                    j->state = 1;
-                    if (i == 0) {
-                        cfg.bin_mode = tmpl[0];
-                        tmpl_ready = true;
-                    }
-                }
-                cv.notify_all();
+    // ---- stage: the parsers (host parse; with the device parse block 0 only,
+    // for the ID template) ----
+    void start_parsers() { for (int t = 0; t < plan.nparse; t++) parsers.emplace_back([this]() { parse_loop(); }); }
+
+    void parse_loop()
+    {
+        for (;;) {
+            int64_t i;
+            Job* j;
+            {
+                std::unique_lock<std::mutex> lk(mu);
+                cv.wait(lk, [&] { return failed || !to_parse.empty() || nblocks >= 0; });
+                if (failed || (to_parse.empty() && nblocks >= 0)) return;
+                i = to_parse.front();
+                to_parse.pop_front();
+                j = jobs[i].get();
             }
-        });
-
-    // early_read: the contexts now, beside the reader's first batch
-    if (early_read) {
-        if (create_contexts()) {
-            reserve();
-            t_ctx = now_s();
-            // (B, the ring and the in-flight bound were sized for C contexts
-            // before they existed: fewer only cost pace, but say so)
-            if ((int64_t)ctxs.size() != C)
-                fprintf(stderr, "seqarc_amd: warning: %zu of %lld encoder contexts created\n", ctxs.size(),
-                        (long long)C);
-        } else {
-            fail(ctx_err);
+            const double tp = st.now();
+            if (!parse_job(*j, pe, pool, texts, plan.dev_parse)) return fail("parse failed");
+            Stamps::add(st.parse_busy, st.now() - tp);
+            if (i == 0) {   // the ID template of the first block
+                const sa_block fb = j->p->view();
+                if (sa_analyze_ids(&fb, pe ? 0 : 1, tmpl) != 0) return fail("ID analysis failed");
+            }
+            if (plan.dev_parse) pool.put(std::move(j->p));   // (only the template needed it)
+            {
+                std::lock_guard<std::mutex> g(mu);
+                j->state = 1;
+                if (i == 0) {
+                    cfg.bin_mode = tmpl[0];
+                    tmpl_ready = true;
+                }
+            }
+            cv.notify_all();
         }
     }
-    // encoders: one host thread per context, batches of B blocks in order
-    auto batch_ready = [&](int64_t k) {   // under mu
-        if (!tmpl_ready) return false;
-        const int64_t b0 = bstart(k);
-        const int64_t b1 = nblocks >= 0 ? std::min(nblocks, bstart(k + 1)) : bstart(k + 1);
-        if (nblocks < 0 && nread < b1) return false;
-        for (int64_t i = b0; i < b1; i++)
+
+    // ---- stage: the encoders, one host thread per context, batches in order ----
+    // By default the stage is part of the context's cycle (WHOLE).  --stage-ahead
+    // measured slower (4.7-5.0 against 6.6-6.7 GB/s on 42.8 GB, round 3 g4d: the
+    // staging contexts' streams outnumber the hardware queues, and the tails
+    // slowed under the concurrent parse); SA_CLI_STREAM: cli_knobs.h.
+    void start_encoders()
+    {
+        const bool have = !dev.ctxs.empty() && dev.ctxs[0];
+        if (plan.dev_parse && !o.ingest_only && o.stage_ahead && have) feed = AHEAD;
+        else if (plan.stream_opt && have) feed = STREAM;
+        for (size_t i = 0; feed == AHEAD && i < dev.ctxs.size(); i++) {
+            sa_ctx* s = sa_create(dev.ctx_dev[i]);
+            sa_input* a = sa_input_empty(dev.ctx_dev[i]);
+            sa_input* b = sa_input_empty(dev.ctx_dev[i]);
+            dev.stagers.push_back(s);
+            dev.sinputs.push_back(a);
+            dev.sinputs.push_back(b);
+            if (!s || !a || !b) {   // (the reader and the parsers run: through fail() and the joins)
+                fail("cannot create the staging contexts");
+                break;
+            }
+            if (plan.ramp) sa_set_reserve(s, (uint32_t)plan.B);
+        }
+        st.enc_start = st.now();
+        // (after a failure every encoder returns from its first claim, before it looks at its staging context)
+        for (size_t ci = 0; ci < dev.ctxs.size(); ci++) encoders.emplace_back([this, ci]() { encode_loop(ci); });
+    }
+
+    // (under mu) the end of batch k: its blocks are [bstart(k), batch_end(k))
+    int64_t batch_end(int64_t k) { return nblocks >= 0 ? std::min(nblocks, plan.bstart(k + 1)) : plan.bstart(k + 1); }
+
+    bool batch_ready(int64_t k)   // under mu
+    {
+        if (!tmpl_ready || (nblocks < 0 && nread < batch_end(k))) return false;
+        for (int64_t i = plan.bstart(k); i < batch_end(k); i++)
             if (jobs.count(i) == 0 || jobs[i]->state < 1) return false;
         return true;
-    };
-    std::vector<std::thread> encoders;
-    // --stage-ahead (device parse): each context stages its next batch into a
-    // second device input -- with a staging context of its own (stream,
-    // mailbox) on a helper thread -- while it encodes the current one, so the
-    // H2D copy and the parse leave the context's cycle.  Measured slower (4.7-5.0
-    // against 6.6-6.7 GB/s on 42.8 GB, round 3 g4d: the staging contexts' streams
-    // outnumber the hardware queues, and the tails slowed under the concurrent
-    // parse), so by default the stage is part of the cycle (sa_stage_text into
-    // the context's own input).
-    const bool stage_ahead = dev_parse && !o.ingest_only && o.stage_ahead && !ctxs.empty() && ctxs[0];
-    std::vector<sa_ctx*> stagers;
-    std::vector<sa_input*> sinputs;   // two per context
-    if (stage_ahead) {
-        for (size_t i = 0; i < ctxs.size(); i++) {
-            sa_ctx* s = sa_create(ctx_dev[i]);
-            sa_input* a = sa_input_empty(ctx_dev[i]);
-            sa_input* b = sa_input_empty(ctx_dev[i]);
-            if (!s || !a || !b) {
-                fprintf(stderr, "seqarc_amd: cannot create the staging contexts\n");
-                return 1;
-            }
-            if (ramp) sa_set_reserve(s, (uint32_t)B);
-            stagers.push_back(s);
-            sinputs.push_back(a);
-            sinputs.push_back(b);
-        }
     }
+
     // takes batch k (in order) once the reader has cut it: false when the input
     // is exhausted or the run failed
-    auto claim = [&](int64_t& k, std::vector<Job*>& js) -> bool {
+    bool claim(int64_t& k, std::vector<Job*>& js)
+    {
         std::unique_lock<std::mutex> lk(mu);
         if (failed) return false;
         k = next_batch++;
-        cv.wait(lk, [&] { return failed || (nblocks >= 0 && bstart(k) >= nblocks) || batch_ready(k); });
-        if (failed || (nblocks >= 0 && bstart(k) >= nblocks)) return false;
-        const int64_t b0 = bstart(k), b1 = nblocks >= 0 ? std::min(nblocks, bstart(k + 1)) : bstart(k + 1);
+        cv.wait(lk, [&] { return failed || (nblocks >= 0 && plan.bstart(k) >= nblocks) || batch_ready(k); });
+        if (failed || (nblocks >= 0 && plan.bstart(k) >= nblocks)) return false;
         js.clear();
-        for (int64_t i = b0; i < b1; i++) js.push_back(jobs[i].get());
+        for (int64_t i = plan.bstart(k); i < batch_end(k); i++) js.push_back(jobs[i].get());
         return true;
-    };
-    // stages the batch's texts into input I with staging context s (the text
-    // windows go back to the reader at once)
-    auto stage_into = [&](sa_ctx* s, sa_input* I, std::vector<Job*>& js) -> bool {
-        const double t0 = now_s();
-        std::vector<sa_text_block> tin(js.size());
+    }
+
+    // STREAM: batch k once its first block is cut (and the ID template known):
+    // false when the input ended before it or the run failed
+    bool claim_first(int64_t& k)
+    {
+        std::unique_lock<std::mutex> lk(mu);
+        if (failed) return false;
+        k = next_batch++;
+        cv.wait(lk, [&] {
+            return failed || (nblocks >= 0 && plan.bstart(k) >= nblocks) || (tmpl_ready && nread > plan.bstart(k));
+        });
+        return !(failed || (nblocks >= 0 && plan.bstart(k) >= nblocks));
+    }
+
+    sa_text_block text_of(const Job& j) const   // a block's text (its second input only with pe)
+    {
+        return sa_text_block{j.t1.data(), j.t1.size(), pe ? j.t2.data() : nullptr, pe ? j.t2.size() : 0};
+    }
+
+    // the batch's texts are on the device: they go back to the reader, the jobs
+    // take what the parse found; by_bound: their output buffers sized by the bound
+    void staged_batch(const std::vector<Job*>& js, const std::vector<sa_text_info>& ti, bool give, bool by_bound)
+    {
+        for (size_t i = 0; i < js.size(); i++) {
+            if (give) give_back(*js[i], texts);   // (the device holds the text now)
+            js[i]->nreads = ti[i].nreads;
+            js[i]->len_long = ti[i].len_long;
+            if (by_bound) outpool.take(js[i]->out, ti[i].out_bound);
+        }
+    }
+
+    // the batch's texts staged (H2D + device parse) since t0 -- WHOLE: into
+    // context c's own input (I null; the output buffers by the bound only with
+    // SA_CLI_OUT_EXACT=0, else by the encoded sizes after the run); AHEAD: into
+    // input I with the staging context c -- and handed back to the reader
+    bool stage(sa_ctx* c, sa_input* I, std::vector<Job*>& js, double t0, bool by_bound)
+    {
+        std::vector<sa_text_block> tin;
+        for (Job* j : js) tin.push_back(text_of(*j));
         std::vector<sa_text_info> ti(js.size());
-        for (size_t i = 0; i < js.size(); i++)
-            tin[i] = sa_text_block{js[i]->t1.data(), js[i]->t1.size(), pe ? js[i]->t2.data() : nullptr,
-                                   pe ? js[i]->t2.size() : 0};
-        if (sa_stage_text_input(s, I, tin.data(), (int)tin.size(), ti.data()) != 0) {
-            fail(std::string("staging failed: ") + sa_last_error(s));
-            return false;
-        }
-        {
-            double cur = stage_busy.load();
-            while (!stage_busy.compare_exchange_weak(cur, cur + now_s() - t0)) {}
-        }
+        if ((I ? sa_stage_text_input(c, I, tin.data(), (int)tin.size(), ti.data())
+               : sa_stage_text(c, tin.data(), (int)tin.size(), ti.data())) != 0)
+            return fail(std::string("staging failed: ") + sa_last_error(c)), false;
+        Stamps::add(st.stage_busy, st.now() - t0);
         {
             std::lock_guard<std::mutex> g(mu);
             staged += (int64_t)js.size();
-            for (size_t i = 0; i < js.size(); i++) {
-                give_back(*js[i], texts);   // (the device holds the text now)
-                js[i]->nreads = ti[i].nreads;
-                js[i]->len_long = ti[i].len_long;
-                outpool.take(js[i]->out, ti[i].out_bound);
-            }
         }
-        cv.notify_all();
+        staged_batch(js, ti, true, by_bound);
+        cv.notify_all();   // (text windows are free for the reader)
         return true;
-    };
-    for (size_t ci = 0; stage_ahead && ci < ctxs.size(); ci++)
-        encoders.emplace_back([&, ci]() {
-            sa_ctx* ctx = ctxs[ci];
-            sa_ctx* stg = stagers[ci];
-            sa_input* in2[2] = {sinputs[2 * ci], sinputs[2 * ci + 1]};
-            int64_t k = 0;
-            std::vector<Job*> js;
-            double tw = now_s();
-            if (!claim(k, js)) return;
-            double te = now_s();
-            if (!stage_into(stg, in2[0], js)) return;
-            for (int cur = 0;; cur ^= 1) {
-                // the next batch is claimed and staged while this one encodes
-                int64_t k2 = -1;
-                std::vector<Job*> js2;
-                double tw2 = 0, te2 = 0;
-                std::future<int> next = std::async(std::launch::async, [&]() -> int {
-                    tw2 = now_s();
-                    if (!claim(k2, js2)) return 0;
-                    te2 = now_s();
-                    return stage_into(stg, in2[cur ^ 1], js2) ? 1 : -1;
-                });
-                {
-                    double c0 = t_first_enc.load();
-                    while (te < c0 && !t_first_enc.compare_exchange_weak(c0, te)) {}
-                }
-                std::vector<sa_out> outs(js.size());
-                for (size_t i = 0; i < js.size(); i++) outs[i] = sa_out{js[i]->out.data(), js[i]->out.size(), 0};
-                const sa_cfg c = cfg;
-                const double tr = now_s();
-                if ((chain ? sa_run_input_aligned(ctx, in2[cur], &c, &acfg[ctx], chain, (uint64_t)k)
-                           : sa_run_input(ctx, in2[cur], &c)) != 0)
-                    return fail(std::string("encode failed: ") + sa_last_error(ctx));
-                const double tf = now_s();
-                if (sa_fetch(ctx, outs.data(), (int)outs.size()) != 0)
-                    return fail(std::string("fetch failed: ") + sa_last_error(ctx));
-                if (o.verbose) {
-                    const char* pn[16];
-                    float pm[16];
-                    const int np = sa_phase_times(ctx, pn, pm, 16);
-                    std::string ph;
-                    for (int x = 0; x < np; x++) {
-                        char pb[48];
-                        snprintf(pb, sizeof pb, " %s %.0f", pn[x], pm[x]);
-                        ph += pb;
-                    }
-                    fprintf(stderr,
-                            "seqarc_amd: batch %lld (%zu blocks) context %p: asked %.3f s, ready %.3f s, staged ahead, "
-                            "run from %.3f s for %.3f s, fetch %.3f s; device ms:%s\n",
-                            (long long)k, js.size(), (void*)ctx, tw, te, tr, tf - tr, now_s() - tf, ph.c_str());
-                }
-                {
-                    const double t1 = now_s();
-                    double c0 = enc_busy.load();
-                    while (!enc_busy.compare_exchange_weak(c0, c0 + t1 - tr)) {}
-                    c0 = t_last_enc.load();
-                    while (t1 > c0 && !t_last_enc.compare_exchange_weak(c0, t1)) {}
-                }
-                {
-                    std::lock_guard<std::mutex> g(mu);
-                    for (size_t i = 0; i < js.size(); i++) {
-                        js[i]->out.n = outs[i].size;
-                        js[i]->state = 2;
-                    }
-                }
-                cv.notify_all();
-                const int r = next.get();
-                if (r <= 0) return;   // (no more batches, or the staging failed: fail() was called)
-                k = k2;
-                js = std::move(js2);
-                tw = tw2;
-                te = te2;
-            }
-        });
-    const double t_enc_start = now_s();
-    // (round 6) the device parse, streamed: a context takes its batch as soon as
-    // the reader has cut the batch's first block and copies each block's text to
-    // the device as it is cut (sa_text_upload: the reader's segments are free
-    // again at once, so the reader is not held to the pace of whole-batch
-    // staging), then parses the batch (sa_text_parse) and encodes it; meanwhile
-    // a helper thread takes the next batch and uploads it into the input's other
-    // text arena, so the next cycle starts with its text already on the device.
-    // SA_CLI_STREAM=1 (A/B; off by default): the reader ran faster with it
-    // (17.8 GB read in 0.69 against 0.92 s, 42.8 GB in 1.84 against 2.39 s) but
-    // the device pipeline slower -- pass R 744-1,019 against 605-694 ms a batch,
-    // the run's end 2.28 / 4.46 against 2.08-2.14 / 3.48-3.59 s (r6e, one box):
-    // with every batch on the device at once the fronts queue up all the same
-    // and the concurrent uploads slow the chains.  By default the round-5 path:
-    // sa_stage_text of a whole batch once the reader has cut it.
-    const bool stream_stage = stream_opt && !stage_ahead && !ctxs.empty() && ctxs[0];
-    // bytes reserved per text on the device: the reader's window (a block's text
-    // never exceeds it) and some slack
-    const uint64_t tstride = (pe ? (uint64_t)((uint32_t)bs >> 1) : bs) + (128u << 10);
-    // batch k once its first block is cut (and the ID template known): false
-    // when the input ended before it or the run failed
-    auto claim_first = [&](int64_t& k) -> bool {
-        std::unique_lock<std::mutex> lk(mu);
-        if (failed) return false;
-        k = next_batch++;
-        cv.wait(lk, [&] { return failed || (nblocks >= 0 && bstart(k) >= nblocks) || (tmpl_ready && nread > bstart(k)); });
-        return !(failed || (nblocks >= 0 && bstart(k) >= nblocks));
-    };
-    // the blocks of batch k to the device (text arena `slot` of ctx's input),
-    // each as soon as the reader has cut it; its text goes back to the reader
-    auto upload = [&](sa_ctx* ctx, int slot, int64_t k, std::vector<Job*>& js) -> bool {
+    }
+
+    // STREAM: the blocks of batch k to the device (text arena `slot` of ctx's
+    // input), each as soon as the reader has cut it; its text goes back to the reader
+    bool upload(sa_ctx* ctx, int slot, int64_t k, std::vector<Job*>& js)
+    {
         js.clear();
-        const int nmax = (int)(bstart(k + 1) - bstart(k));
-        for (int64_t i = bstart(k); i < bstart(k + 1); i++) {
+        const int64_t b0 = plan.bstart(k), b1 = plan.bstart(k + 1);
+        for (int64_t i = b0; i < b1; i++) {
             Job* j;
             {
                 std::unique_lock<std::mutex> lk(mu);
@@ -2648,389 +2544,330 @@ int compress(const Options& o)
                 if (nblocks >= 0 && i >= nblocks) break;
                 j = jobs[i].get();
             }
-            const sa_text_block tb{j->t1.data(), j->t1.size(), pe ? j->t2.data() : nullptr, pe ? j->t2.size() : 0};
-            const double t0 = now_s();
-            if (sa_text_upload(ctx, nullptr, slot, (int)(i - bstart(k)), nmax, &tb, tstride) != 0) {
-                fail(std::string("staging failed: ") + sa_last_error(ctx));
-                return false;
-            }
+            const sa_text_block tb = text_of(*j);
+            const double t0 = st.now();
+            if (sa_text_upload(ctx, nullptr, slot, (int)(i - b0), (int)(b1 - b0), &tb, plan.tstride) != 0)
+                return fail(std::string("staging failed: ") + sa_last_error(ctx)), false;
             give_back(*j, texts);   // (the device holds the text now)
             {
                 std::lock_guard<std::mutex> g(mu);
                 staged++;
-                double cur = stage_busy.load();
-                while (!stage_busy.compare_exchange_weak(cur, cur + now_s() - t0)) {}
+                Stamps::add(st.stage_busy, st.now() - t0);
             }
             cv.notify_all();
             js.push_back(j);
         }
         return true;
-    };
-    static const char kPe = 0;   // (a non-NULL text2 marks a PE block for sa_text_parse)
-    const bool prefetch = !(std::getenv("SA_CLI_PREFETCH") && std::atoi(std::getenv("SA_CLI_PREFETCH")) == 0);
-    for (size_t ci = 0; stream_stage && ci < ctxs.size(); ci++)
-        encoders.emplace_back([&, ctx = ctxs[ci]]() {
-            int slot = 0;
-            int64_t k = -1;
-            std::vector<Job*> js;
-            double tw = now_s();
-            if (!claim_first(k) || !upload(ctx, slot, k, js)) return;
-            double te = now_s();
-            for (;;) {
-                const double tp = now_s();
-                std::vector<sa_text_block> lens(js.size());
-                std::vector<sa_text_info> ti(js.size());
-                for (size_t i = 0; i < js.size(); i++)
-                    lens[i] = sa_text_block{nullptr, js[i]->text1, pe ? reinterpret_cast<const uint8_t*>(&kPe) : nullptr,
-                                            pe ? js[i]->text2 : 0};
-                if (sa_text_parse(ctx, nullptr, slot, lens.data(), (int)js.size(), tstride, ti.data()) != 0)
-                    return fail(std::string("staging failed: ") + sa_last_error(ctx));
-                std::vector<sa_out> outs(js.size());
-                for (size_t i = 0; i < js.size(); i++) {
-                    js[i]->nreads = ti[i].nreads;
-                    js[i]->len_long = ti[i].len_long;
-                    outpool.take(js[i]->out, ti[i].out_bound);
-                    outs[i] = sa_out{js[i]->out.data(), js[i]->out.size(), 0};
-                }
-                // the next batch into the other arena while this one encodes
-                // (SA_CLI_PREFETCH=0: after it, A/B)
-                int64_t k2 = -1;
-                std::vector<Job*> js2;
-                double tw2 = 0, te2 = 0;
-                auto take_next = [&, slot2 = slot ^ 1]() -> int {
-                    tw2 = now_s();
-                    if (!claim_first(k2)) return 0;
-                    const bool ok = upload(ctx, slot2, k2, js2);
-                    te2 = now_s();
-                    return ok ? 1 : -1;
-                };
-                std::future<int> next;
-                if (prefetch) next = std::async(std::launch::async, take_next);
-                {
-                    double c0 = t_first_enc.load();
-                    while (te < c0 && !t_first_enc.compare_exchange_weak(c0, te)) {}
-                }
-                const sa_cfg c = cfg;
-                const double tr = now_s();
-                if ((chain ? sa_run_aligned(ctx, &c, &acfg[ctx], chain, (uint64_t)k) : sa_run(ctx, &c)) != 0)
-                    return fail(std::string("encode failed: ") + sa_last_error(ctx));
-                const double tf = now_s();
-                if (sa_fetch(ctx, outs.data(), (int)outs.size()) != 0)
-                    return fail(std::string("fetch failed: ") + sa_last_error(ctx));
-                if (o.verbose) {
-                    const char* pn[16];
-                    float pm[16];
-                    const int np = sa_phase_times(ctx, pn, pm, 16);
-                    std::string ph;
-                    for (int x = 0; x < np; x++) {
-                        char pb[48];
-                        snprintf(pb, sizeof pb, " %s %.0f", pn[x], pm[x]);
-                        ph += pb;
-                    }
-                    fprintf(stderr,
-                            "seqarc_amd: batch %lld (%zu blocks) context %p: asked %.3f s, uploaded %.3f s, parse %.3f s, "
-                            "run %.3f s, fetch %.3f s; device ms:%s\n",
-                            (long long)k, js.size(), (void*)ctx, tw, te, tr - tp, tf - tr, now_s() - tf, ph.c_str());
-                }
-                {
-                    const double t1 = now_s();
-                    double c0 = enc_busy.load();
-                    while (!enc_busy.compare_exchange_weak(c0, c0 + t1 - tp)) {}
-                    c0 = t_last_enc.load();
-                    while (t1 > c0 && !t_last_enc.compare_exchange_weak(c0, t1)) {}
-                }
-                {
-                    std::lock_guard<std::mutex> g(mu);
-                    for (size_t i = 0; i < js.size(); i++) {
-                        js[i]->out.n = outs[i].size;
-                        js[i]->state = 2;
-                    }
-                }
-                cv.notify_all();
-                const int r = prefetch ? next.get() : take_next();
-                if (r <= 0) return;   // (no more batches, or the upload failed: fail() was called)
-                k = k2;
-                js = std::move(js2);
-                slot ^= 1;
-                tw = tw2;
-                te = te2;
-            }
-        });
-    for (size_t ci = 0; !stage_ahead && !stream_stage && ci < ctxs.size(); ci++)
-        encoders.emplace_back([&, ctx = ctxs[ci]]() {
-            for (;;) {
-                int64_t k, b0, b1;
-                std::vector<Job*> js;
-                const double tw = now_s();
-                {
-                    std::unique_lock<std::mutex> lk(mu);
-                    if (failed) return;
-                    k = next_batch++;
-                    cv.wait(lk, [&] { return failed || (nblocks >= 0 && bstart(k) >= nblocks) || batch_ready(k); });
-                    if (failed || (nblocks >= 0 && bstart(k) >= nblocks)) return;
-                    b0 = bstart(k);
-                    b1 = nblocks >= 0 ? std::min(nblocks, bstart(k + 1)) : bstart(k + 1);
-                    for (int64_t i = b0; i < b1; i++) js.push_back(jobs[i].get());
-                }
-                std::vector<sa_out> outs(js.size());
-                const sa_cfg c = cfg;
-                const double te = now_s();
-                {
-                    double cur = t_first_enc.load();
-                    while (te < cur && !t_first_enc.compare_exchange_weak(cur, te)) {}
-                }
-                if (dev_parse && !ctx) {   // --ingest-only: the batch is taken, its windows recycled
-                    for (size_t i = 0; i < js.size(); i++) {
-                        if (o.ingest_crc) {   // (a check of the delivered bytes, for the tests: CPU work no device path does)
-                            uint32_t c = (uint32_t)crc32(0L, js[i]->t1.data(), (uInt)js[i]->t1.size());
-                            if (pe) c = (uint32_t)crc32(c, js[i]->t2.data(), (uInt)js[i]->t2.size());
-                            js[i]->crc = c;
-                        }
-                        give_back(*js[i], texts);
-                        outs[i] = sa_out{nullptr, 0, 0};
-                    }
-                    {
-                        std::lock_guard<std::mutex> g(mu);
-                        staged += (int64_t)js.size();
-                    }
-                    cv.notify_all();
-                } else if (dev_parse) {
-                    std::vector<sa_text_block> tin(js.size());
-                    std::vector<sa_text_info> ti(js.size());
-                    for (size_t i = 0; i < js.size(); i++)
-                        tin[i] = sa_text_block{js[i]->t1.data(), js[i]->t1.size(), pe ? js[i]->t2.data() : nullptr,
-                                               pe ? js[i]->t2.size() : 0};
-                    if (sa_stage_text(ctx, tin.data(), (int)tin.size(), ti.data()) != 0)
-                        return fail(std::string("staging failed: ") + sa_last_error(ctx));
-                    {
-                        const double ts = now_s() - te;
-                        double cur = stage_busy.load();
-                        while (!stage_busy.compare_exchange_weak(cur, cur + ts)) {}
-                    }
-                    {
-                        std::lock_guard<std::mutex> g(mu);
-                        staged += (int64_t)js.size();
-                    }
-                    for (size_t i = 0; i < js.size(); i++) {
-                        give_back(*js[i], texts);   // (the device holds the text now)
-                        js[i]->nreads = ti[i].nreads;
-                        js[i]->len_long = ti[i].len_long;
-                        if (!out_exact) {
-                            outpool.take(js[i]->out, ti[i].out_bound);
-                            outs[i] = sa_out{js[i]->out.data(), js[i]->out.size(), 0};
-                        }
-                    }
-                    cv.notify_all();   // (text windows are free for the reader)
-                    const double tr = now_s();
-                    if ((chain ? sa_run_aligned(ctx, &c, &acfg[ctx], chain, (uint64_t)k) : sa_run(ctx, &c)) != 0)
-                        return fail(std::string("encode failed: ") + sa_last_error(ctx));
-                    if (out_exact) {   // the output buffers sized by the encoded blocks
-                        std::vector<uint64_t> fs(js.size());
-                        if (sa_fetch_sizes(ctx, fs.data(), (int)fs.size()) != 0)
-                            return fail(std::string("fetch failed: ") + sa_last_error(ctx));
-                        for (size_t i = 0; i < js.size(); i++) {
-                            outpool.take(js[i]->out, fs[i]);
-                            outs[i] = sa_out{js[i]->out.data(), js[i]->out.size(), 0};
-                        }
-                    }
-                    const double tf = now_s();
-                    if (sa_fetch(ctx, outs.data(), (int)outs.size()) != 0)
-                        return fail(std::string("fetch failed: ") + sa_last_error(ctx));
-                    if (o.verbose) {   // per batch: when it became ready, what each step took, device phases
-                        const char* pn[16];
-                        float pm[16];
-                        const int np = sa_phase_times(ctx, pn, pm, 16);
-                        std::string ph;
-                        for (int x = 0; x < np; x++) {
-                            char pb[48];
-                            snprintf(pb, sizeof pb, " %s %.0f", pn[x], pm[x]);
-                            ph += pb;
-                        }
-                        uint32_t grows = 0;
-                        double alloc_ms = 0;
-                        sa_alloc_stats(&grows, &alloc_ms);
-                        fprintf(stderr,
-                                "seqarc_amd: batch %lld (%zu blocks) context %p: asked %.3f s, ready %.3f s, stage %.3f s, "
-                                "run %.3f s, fetch %.3f s; grows %u, alloc %.0f ms; device ms:%s\n",
-                                (long long)k, js.size(), (void*)ctx, tw, te, tr - te, tf - tr, now_s() - tf, grows, alloc_ms,
-                                ph.c_str());
-                    }
-                } else {
-                    std::vector<sa_block> in(js.size());
-                    for (size_t i = 0; i < js.size(); i++) {
-                        in[i] = js[i]->p->view();
-                        outpool.take(js[i]->out, sa_output_bound(&in[i]));   // (uninitialised: only the real bytes are touched)
-                        outs[i] = sa_out{js[i]->out.data(), js[i]->out.size(), 0};
-                    }
-                    if (!ctx) {   // --host-only
-                        // (tests: SA_CLI_TEST_OUT=n gives each block n bytes of filler, so the
-                        // archive writer runs without a device)
-                        static const uint64_t test_out =
-                            std::getenv("SA_CLI_TEST_OUT") ? std::strtoull(std::getenv("SA_CLI_TEST_OUT"), nullptr, 10) : 0;
-                        for (sa_out& x : outs) {
-                            x.size = std::min<uint64_t>(test_out, x.cap);
-                            if (x.size) memset(x.data, 0x5a, x.size);
-                        }
-                    } else if (chain) {   // (the batch's place in the chain: k)
-                        if (sa_stage(ctx, in.data(), (int)in.size()) != 0 ||
-                            sa_run_aligned(ctx, &c, &acfg[ctx], chain, (uint64_t)k) != 0 ||
-                            sa_fetch(ctx, outs.data(), (int)outs.size()) != 0)
-                            return fail(std::string("encode failed: ") + sa_last_error(ctx));
-                    } else if (sa_encode_blocks(ctx, in.data(), (int)in.size(), &c, outs.data()) != 0)
-                        return fail(std::string("encode failed: ") + sa_last_error(ctx));
-                }
-                {
-                    const double tf = now_s();
-                    double cur = enc_busy.load();
-                    while (!enc_busy.compare_exchange_weak(cur, cur + tf - te)) {}
-                    cur = t_last_enc.load();
-                    while (tf > cur && !t_last_enc.compare_exchange_weak(cur, tf)) {}
-                }
-                {
-                    std::lock_guard<std::mutex> g(mu);
-                    for (size_t i = 0; i < js.size(); i++) {
-                        js[i]->out.n = outs[i].size;
-                        js[i]->state = 2;
-                    }
-                }
-                cv.notify_all();
-            }
-        });
+    }
 
-    // writer (this thread): blocks in input order, each handed to the archive
-    // writer's threads at its offset (ArcWriter); `written` counts the blocks
-    // whose copy is done (the reader's bound on blocks in flight)
-    int rc = 0;
-    std::vector<sa_arc_block> info;
-    uint64_t total = 0;
-    uint32_t text_crc = 0;
-    uint8_t hdr[16] = {0};
-    ArcWriter aw;
-    const int nwriters = std::max(1, std::min(8, o.writers));
-    const bool opened = aw.open(path, nwriters, [&](std::unique_ptr<Job> j) {
-        if (j->p) pool.put(std::move(j->p));
-        outpool.give(j->out);
-        j.reset();
-        {
-            std::lock_guard<std::mutex> g(mu);
-            written++;
-        }
-        cv.notify_all();
-    });
-    if (!opened || !aw.lead(hdr, 16))   // patched at the end (createOutFile@0x417480 / writeFileInfo@0x4171b0)
-        fail("cannot write " + path);
-    for (int64_t i = 0;; i++) {
-        std::unique_ptr<Job> j;
-        {
-            std::unique_lock<std::mutex> lk(mu);
-            cv.wait(lk, [&] {
-                return failed || (nblocks >= 0 && i >= nblocks) || (jobs.count(i) && jobs[i]->state == 2);
-            });
-            if (failed || (nblocks >= 0 && i >= nblocks)) break;
-            j = std::move(jobs[i]);
-            jobs.erase(i);
-        }
-        if (aw.bad()) {   // writeData@0x40e070: exit(1)
-            fail("write error on " + path);
-            break;
-        }
-        info.push_back(sa_arc_block{(uint32_t)j->out.size(), j->len_long, j->text1, j->text2});
-        text_crc = (uint32_t)crc32_combine(text_crc, j->crc, (z_off_t)(j->text1 + j->text2));
-        const uint64_t off = 16 + total;
-        total += j->out.size();
-        aw.put(std::move(j), off);
+    // STREAM: the uploaded batch parsed on the device, the output buffers by the bound
+    bool parse_streamed(sa_ctx* ctx, int slot, Turn& t)
+    {
+        static const char kPe = 0;   // (a non-NULL text2 marks a PE block for sa_text_parse)
+        std::vector<sa_text_block> lens(t.js.size());
+        std::vector<sa_text_info> ti(t.js.size());
+        for (size_t i = 0; i < t.js.size(); i++)
+            lens[i] = sa_text_block{nullptr, t.js[i]->text1, pe ? reinterpret_cast<const uint8_t*>(&kPe) : nullptr,
+                                    pe ? t.js[i]->text2 : 0};
+        if (sa_text_parse(ctx, nullptr, slot, lens.data(), (int)t.js.size(), plan.tstride, ti.data()) != 0)
+            return fail(std::string("staging failed: ") + sa_last_error(ctx)), false;
+        staged_batch(t.js, ti, false, true);
+        return true;
     }
-    const double t_written = now_s();
-    reader.join();
-    for (auto& t : parsers) t.join();
-    for (auto& t : encoders) t.join();
-    if (seg_free.joinable()) {
-        {
-            std::lock_guard<std::mutex> g(mu);
-            seg_stop = true;   // (wakes it when the run ended early)
-            cv.notify_all();
+
+    // the feed: the encoder's (or its helper's) next batch, as far towards the
+    // device as the feed takes it outside the cycle.  1: t holds a batch, 0: no
+    // more batches, -1: failed (fail() was called)
+    int take(size_t ci, int slot, Turn& t)
+    {
+        t.asked = st.now();
+        if (feed == STREAM) {
+            if (!claim_first(t.k)) return 0;
+            const bool ok = upload(dev.ctxs[ci], slot, t.k, t.js);
+            t.ready = st.now();
+            return ok ? 1 : -1;
         }
-        seg_free.join();
-    }
-    const double t_joined = now_s();
-    // the archive is finished (trailer, header, closed) before the contexts'
-    // device buffers are released (~1.4 s for five contexts' ~200 GB)
-    auto release = [&]() {
-        for (sa_hash_index* ix : indexes) sa_hash_destroy(ix);
-        indexes.clear();
-        if (chain) sa_align_chain_destroy(chain);
-        chain = nullptr;
-        for (sa_input*& I : sinputs) {
-            sa_input_destroy(I);
-            I = nullptr;
-        }
-        for (sa_ctx*& s : stagers) {
-            sa_destroy(s);
-            s = nullptr;
-        }
-        for (sa_ctx*& c : ctxs)
-            if (c) {
-                sa_destroy(c);
-                c = nullptr;
-            }
-    };
-    if (failed) {
-        aw.finish(nullptr, 0, 0, nullptr, 0);
-        release();
-        fprintf(stderr, "seqarc_amd: %s\n", err.c_str());
+        if (!claim(t.k, t.js)) return 0;
+        t.ready = st.now();
+        if (feed == AHEAD && !stage(dev.stagers[ci], dev.sinputs[2 * ci + (size_t)slot], t.js, t.ready, true)) return -1;
         return 1;
     }
-    sa_arc_info ai{o.f1, pe ? o.f2 : nullptr, pe ? 1 : 0, in1.is_gz ? 1 : 0, plus_bare, cfg.md5,
-                   cfg.lossy > 0.0 ? 1 : 0, tmpl, o.ref ? rf.md5 : nullptr, (uint32_t)o.insert};
-    std::vector<uint8_t> tr(4096 + 40 * info.size());
-    const int64_t tl = sa_arc_trailer2(&ai, o.maxmis, info.data(), (uint32_t)info.size(), tr.data(), tr.size());
-    if (tl < 0) {
-        fprintf(stderr, "seqarc_amd: trailer failed\n");
-        rc = 1;
-    } else {
-        sa_arc_header(total, hdr);
-    }
-    if (!aw.finish(tl < 0 ? nullptr : tr.data(), tl < 0 ? 0 : (size_t)tl, 16 + total, tl < 0 ? nullptr : hdr, 16)) {
-        if (tl >= 0) fprintf(stderr, "seqarc_amd: write error on %s\n", path.c_str());
-        rc = 1;
-    }
-    const double t_closed = now_s();
-    // (diagnostics, SA_CLI_EXIT_PROBE=1: what the exit would tear down, timed
-    // here instead -- the output pool's buffers, then the contexts)
-    if (std::getenv("SA_CLI_EXIT_PROBE") && std::atoi(std::getenv("SA_CLI_EXIT_PROBE")) != 0) {
-        size_t nb = 0, cap = 0;
-        const double p0 = now_s();
-        {
-            std::lock_guard<std::mutex> g(outpool.mu);
-            nb = outpool.free.size();
-            for (auto& b : outpool.free) cap += b.cap;
-            outpool.free.clear();
+
+    int run(size_t ci, int slot, const sa_cfg& c, int64_t k)   // (the batch's place in the chain: k)
+    {
+        sa_ctx* ctx = dev.ctxs[ci];
+        if (feed == AHEAD) {
+            sa_input* I = dev.sinputs[2 * ci + (size_t)slot];
+            return dev.chain ? sa_run_input_aligned(ctx, I, &c, &dev.acfg[ci], dev.chain, (uint64_t)k) : sa_run_input(ctx, I, &c);
         }
-        const double p1 = now_s();
-        release();
-        const double p2 = now_s();
-        fprintf(stderr, "seqarc_amd: exit probe: output pool %zu buffers, %.3f GB reserved, freed in %.3f s; contexts "
-                        "released in %.3f s\n", nb, (double)cap / 1e9, p1 - p0, p2 - p1);
+        return dev.chain ? sa_run_aligned(ctx, &c, &dev.acfg[ci], dev.chain, (uint64_t)k) : sa_run(ctx, &c);
     }
-    // the contexts' device buffers (~200 GB for five contexts) are left to the
-    // process exit unless --release: the command line exits right after this
-    // (main, g_fast_exit), and the driver reclaims them without the ~1.4 s of
-    // hipFree calls (round 3 g3n)
-    if (o.release) release();
-    else g_fast_exit = true;
-    const double secs = std::chrono::duration<double>(std::chrono::steady_clock::now() - t_start).count();
-    if (o.verbose)
-        fprintf(stderr, "seqarc_amd: blocks written %.3f s, segment ring freed %.3f s, encoders done %.3f s, archive closed %.3f s, contexts %s %.3f s\n",
-                t_written, t_seg_freed.load(), t_joined, t_closed, o.release ? "released" : "left to the exit", secs);
-    if (tl >= 0) {
+
+    static void point_outs(const std::vector<Job*>& js, std::vector<sa_out>& outs)
+    {
+        for (size_t i = 0; i < js.size(); i++) outs[i] = sa_out{js[i]->out.data(), js[i]->out.size(), 0};
+    }
+
+    // a batch with no device parse behind it: --ingest-only (the batch is taken,
+    // its windows recycled), --host-only, --host-parse.  false: fail() was called
+    bool host_batch(size_t ci, const sa_cfg& c, Turn& t, std::vector<sa_out>& outs)
+    {
+        sa_ctx* ctx = dev.ctxs[ci];
+        std::vector<Job*>& js = t.js;
+        if (plan.dev_parse) {
+            for (size_t i = 0; i < js.size(); i++) {
+                if (o.ingest_crc) {   // (a check of the delivered bytes, for the tests: CPU work no device path does)
+                    uint32_t x = (uint32_t)crc32(0L, js[i]->t1.data(), (uInt)js[i]->t1.size());
+                    if (pe) x = (uint32_t)crc32(x, js[i]->t2.data(), (uInt)js[i]->t2.size());
+                    js[i]->crc = x;
+                }
+                give_back(*js[i], texts);
+            }
+            {
+                std::lock_guard<std::mutex> g(mu);
+                staged += (int64_t)js.size();
+            }
+            cv.notify_all();
+            return true;
+        }
+        std::vector<sa_block> in(js.size());
+        for (size_t i = 0; i < js.size(); i++) {
+            in[i] = js[i]->p->view();
+            outpool.take(js[i]->out, sa_output_bound(&in[i]));   // (uninitialised: only the real bytes are touched)
+        }
+        point_outs(js, outs);
+        if (!ctx) {   // --host-only (SA_CLI_TEST_OUT=n: n bytes of filler a block)
+            for (sa_out& x : outs) {
+                x.size = std::min<uint64_t>(kn.test_out, x.cap);
+                if (x.size) memset(x.data, 0x5a, x.size);
+            }
+        } else if (dev.chain) {
+            if (sa_stage(ctx, in.data(), (int)in.size()) != 0 || run(ci, 0, c, t.k) != 0 ||
+                sa_fetch(ctx, outs.data(), (int)outs.size()) != 0)
+                return fail(std::string("encode failed: ") + sa_last_error(ctx)), false;
+        } else if (sa_encode_blocks(ctx, in.data(), (int)in.size(), &c, outs.data()) != 0)
+            return fail(std::string("encode failed: ") + sa_last_error(ctx)), false;
+        return true;
+    }
+
+    // (-v) per batch: when it became ready, what each step took, device phases;
+    // each feed has its own wording.  tp / tr / tf: the parse, run and fetch began
+    void batch_line(sa_ctx* ctx, const Turn& t, double tp, double tr, double tf)
+    {
+        const char* pn[16];
+        float pm[16];
+        const int np = sa_phase_times(ctx, pn, pm, 16);
+        std::string ph;
+        for (int x = 0; x < np; x++) {
+            char pb[48];
+            snprintf(pb, sizeof pb, " %s %.0f", pn[x], pm[x]);
+            ph += pb;
+        }
+        char steps[200];
+        const double fetch = st.now() - tf;
+        if (feed == AHEAD) {
+            snprintf(steps, sizeof steps, "ready %.3f s, staged ahead, run from %.3f s for %.3f s, fetch %.3f s", t.ready, tr,
+                     tf - tr, fetch);
+        } else if (feed == STREAM) {
+            snprintf(steps, sizeof steps, "uploaded %.3f s, parse %.3f s, run %.3f s, fetch %.3f s", t.ready, tr - tp, tf - tr,
+                     fetch);
+        } else {
+            uint32_t grows = 0;
+            double alloc_ms = 0;
+            sa_alloc_stats(&grows, &alloc_ms);
+            snprintf(steps, sizeof steps, "ready %.3f s, stage %.3f s, run %.3f s, fetch %.3f s; grows %u, alloc %.0f ms", t.ready,
+                     tr - t.ready, tf - tr, fetch, grows, alloc_ms);
+        }
+        fprintf(stderr, "seqarc_amd: batch %lld (%zu blocks) context %p: asked %.3f s, %s; device ms:%s\n", (long long)t.k,
+                t.js.size(), (void*)ctx, t.asked, steps, ph.c_str());
+    }
+
+    // one context's encoder: take (the feed), run, size and fetch, the -v line,
+    // account, publish.  With a feed that works ahead, a helper thread takes
+    // the next batch into the alternate input / arena (slot ^ 1) meanwhile.
+    void encode_loop(size_t ci)
+    {
+        sa_ctx* ctx = dev.ctxs[ci];
+        const bool device = ctx && plan.dev_parse;
+        const bool helper = feed == AHEAD || (feed == STREAM && kn.prefetch);   // (SA_CLI_PREFETCH=0: after the batch, A/B)
+        Turn cur;
+        if (take(ci, 0, cur) <= 0) return;
+        for (int slot = 0;; slot ^= 1) {
+            const double tp = st.now();
+            if (feed == STREAM && !parse_streamed(ctx, slot, cur)) return;
+            Turn nxt;
+            std::future<int> ahead;   // (declared after nxt: waited for before nxt goes)
+            if (helper) ahead = std::async(std::launch::async, [&, s2 = slot ^ 1]() { return take(ci, s2, nxt); });
+            Stamps::set_min(st.first_enc, cur.ready);
+            std::vector<sa_out> outs(cur.js.size());
+            const sa_cfg c = cfg;
+            double busy_from = cur.ready;   // the feed's own start of its busy interval: ready, run or parse
+            if (!device) {
+                if (!host_batch(ci, c, cur, outs)) return;
+            } else {
+                if (feed == WHOLE && !stage(ctx, nullptr, cur.js, cur.ready, !kn.out_exact)) return;
+                point_outs(cur.js, outs);
+                const double tr = st.now();
+                if (run(ci, slot, c, cur.k) != 0) return fail(std::string("encode failed: ") + sa_last_error(ctx));
+                if (feed == WHOLE && kn.out_exact) {   // the output buffers sized by the encoded blocks
+                    std::vector<uint64_t> fs(cur.js.size());
+                    if (sa_fetch_sizes(ctx, fs.data(), (int)fs.size()) != 0)
+                        return fail(std::string("fetch failed: ") + sa_last_error(ctx));
+                    for (size_t i = 0; i < fs.size(); i++) outpool.take(cur.js[i]->out, fs[i]);
+                    point_outs(cur.js, outs);
+                }
+                const double tf = st.now();
+                if (sa_fetch(ctx, outs.data(), (int)outs.size()) != 0)
+                    return fail(std::string("fetch failed: ") + sa_last_error(ctx));
+                if (o.verbose) batch_line(ctx, cur, tp, tr, tf);
+                if (feed != WHOLE) busy_from = feed == AHEAD ? tr : tp;
+            }
+            const double t1 = st.now();
+            Stamps::add(st.enc_busy, t1 - busy_from);
+            Stamps::set_max(st.last_enc, t1);
+            {
+                std::lock_guard<std::mutex> g(mu);
+                for (size_t i = 0; i < cur.js.size(); i++) {
+                    cur.js[i]->out.n = outs[i].size;
+                    cur.js[i]->state = 2;
+                }
+            }
+            cv.notify_all();
+            const int r = helper ? ahead.get() : take(ci, slot ^ 1, nxt);
+            if (r <= 0) return;   // (no more batches, or the feed failed: fail() was called)
+            cur = std::move(nxt);
+        }
+    }
+
+    // ---- stage: the writer (this thread): blocks in input order, each handed to
+    // the archive writer's threads at its offset (ArcWriter); `written` counts
+    // the blocks whose copy is done (the reader's bound on blocks in flight) ----
+    void write_blocks()
+    {
+        const bool opened = aw.open(path, std::max(1, std::min(8, o.writers)), [this](std::unique_ptr<Job> j) {
+            if (j->p) pool.put(std::move(j->p));
+            outpool.give(j->out);
+            j.reset();
+            {
+                std::lock_guard<std::mutex> g(mu);
+                written++;
+            }
+            cv.notify_all();
+        });
+        if (!opened || !aw.lead(hdr, 16))   // patched at the end (createOutFile@0x417480 / writeFileInfo@0x4171b0)
+            fail("cannot write " + path);
+        for (int64_t i = 0;; i++) {
+            std::unique_ptr<Job> j;
+            {
+                std::unique_lock<std::mutex> lk(mu);
+                cv.wait(lk, [&] {
+                    return failed || (nblocks >= 0 && i >= nblocks) || (jobs.count(i) && jobs[i]->state == 2);
+                });
+                if (failed || (nblocks >= 0 && i >= nblocks)) break;
+                j = std::move(jobs[i]);
+                jobs.erase(i);
+            }
+            if (aw.bad()) {   // writeData@0x40e070: exit(1)
+                fail("write error on " + path);
+                break;
+            }
+            info.push_back(sa_arc_block{(uint32_t)j->out.size(), j->len_long, j->text1, j->text2});
+            text_crc = (uint32_t)crc32_combine(text_crc, j->crc, (z_off_t)(j->text1 + j->text2));
+            const uint64_t off = 16 + total;
+            total += j->out.size();
+            aw.put(std::move(j), off);
+        }
+        st.written = st.now();
+    }
+
+    // ---- stage: every thread joined (after a failure too: fail() wakes them all) ----
+    void join()
+    {
+        reader.join();
+        for (auto& t : parsers) t.join();
+        for (auto& t : encoders) t.join();
+        if (seg_free.joinable()) {
+            {
+                std::lock_guard<std::mutex> g(mu);
+                seg_stop = true;   // (wakes it when the run ended early)
+                cv.notify_all();
+            }
+            seg_free.join();
+        }
+        st.joined = st.now();
+    }
+
+    // ---- stage: the trailer and the header, the archive closed -- before the
+    // contexts' device buffers are released (~1.4 s for five contexts' ~200 GB).
+    // false: the run failed (its message printed, the buffers released) ----
+    bool finish_archive()
+    {
+        if (failed) {
+            aw.finish(nullptr, 0, 0, nullptr, 0);
+            dev.release();
+            fprintf(stderr, "seqarc_amd: %s\n", err.c_str());
+            return false;
+        }
+        sa_arc_info ai{o.f1, pe ? o.f2 : nullptr, pe ? 1 : 0, in1.is_gz ? 1 : 0, plus_bare, cfg.md5,
+                       cfg.lossy > 0.0 ? 1 : 0, tmpl, o.ref ? rf.md5 : nullptr, (uint32_t)o.insert};
+        std::vector<uint8_t> tr(4096 + 40 * info.size());
+        tl = sa_arc_trailer2(&ai, o.maxmis, info.data(), (uint32_t)info.size(), tr.data(), tr.size());
+        if (tl < 0) {
+            fprintf(stderr, "seqarc_amd: trailer failed\n");
+            rc = 1;
+        } else {
+            sa_arc_header(total, hdr);
+        }
+        if (!aw.finish(tl < 0 ? nullptr : tr.data(), tl < 0 ? 0 : (size_t)tl, 16 + total, tl < 0 ? nullptr : hdr, 16)) {
+            if (tl >= 0) fprintf(stderr, "seqarc_amd: write error on %s\n", path.c_str());
+            rc = 1;
+        }
+        st.closed = st.now();
+        return true;
+    }
+
+    // ---- stage: the contexts' device buffers (~200 GB for five contexts) are
+    // left to the process exit unless --release: the command line exits right
+    // after this (compress, g_fast_exit), and the driver reclaims them without
+    // the ~1.4 s of hipFree calls (round 3 g3n) ----
+    void release_or_leave()
+    {
+        if (kn.exit_probe) {   // (diagnostics: what the exit would tear down, timed here instead)
+            size_t nb = 0, cap = 0;
+            const double p0 = st.now();
+            {
+                std::lock_guard<std::mutex> g(outpool.mu);
+                nb = outpool.free.size();
+                for (auto& b : outpool.free) cap += b.cap;
+                outpool.free.clear();
+            }
+            const double p1 = st.now();
+            dev.release();
+            const double p2 = st.now();
+            fprintf(stderr, "seqarc_amd: exit probe: output pool %zu buffers, %.3f GB reserved, freed in %.3f s; contexts "
+                            "released in %.3f s\n", nb, (double)cap / 1e9, p1 - p0, p2 - p1);
+        }
+        if (o.release) dev.release();
+        else dev.leave_to_exit();
+        g_fast_exit = !o.release;
+    }
+
+    // ---- stage: the -v lines and the summary ----
+    void report()
+    {
+        const double secs = st.now();
+        if (o.verbose)
+            fprintf(stderr, "seqarc_amd: blocks written %.3f s, segment ring freed %.3f s, encoders done %.3f s, archive closed %.3f s, contexts %s %.3f s\n",
+                    st.written, st.seg_freed.load(), st.joined, st.closed, o.release ? "released" : "left to the exit", secs);
+        if (tl < 0) return;
         if (o.verbose)
             fprintf(stderr,
                     "seqarc_amd: contexts ready %.3f s, encoders started %.3f s, input read %.3f s, first encode %.3f s, last encode "
                     "done %.3f s; encode busy %.3f s over %zu contexts, parse busy %.3f s over %d threads; "
                     "reader: fill %.3f s, cut %.3f s; stage %.3f s (%s parse)\n",
-                    t_ctx, t_enc_start, t_read_done.load(), t_first_enc.load(), t_last_enc.load(), enc_busy.load(), ctxs.size(),
-                    parse_busy.load(), nparse, fill_busy, cut_busy, stage_busy.load(),
-                    dev_parse ? "device" : "host");
+                    st.ctx, st.enc_start, st.read_done.load(), st.first_enc.load(), st.last_enc.load(), st.enc_busy.load(),
+                    dev.ctxs.size(), st.parse_busy.load(), plan.nparse, st.fill_busy, st.cut_busy, st.stage_busy.load(),
+                    plan.dev_parse ? "device" : "host");
         if (o.verbose && texts.pinned) {
             size_t nch;
             {
@@ -3038,7 +2875,7 @@ int compress(const Options& o)
                 nch = texts.chunks.size();
             }
             fprintf(stderr, "seqarc_amd: text windows: %zu chunks of %zu pinned (%zu ahead, %u on demand, the last at "
-                            "%.3f s)\n", nch, TextPool::kChunk, prefill_chunks, texts.on_demand.load(),
+                            "%.3f s)\n", nch, TextPool::kChunk, plan.prefill_chunks, texts.on_demand.load(),
                     texts.last_on_demand.load());
         }
         if (o.ingest_only) fprintf(stderr, "seqarc_amd: ingest text crc32 %08x\n", text_crc);
@@ -3046,9 +2883,31 @@ int compress(const Options& o)
                 (unsigned long long)total_in, (unsigned long long)(16 + total + tl),
                 (double)total_in / (double)(16 + total + tl), secs, (double)total_in / secs / 1e6);
     }
-    if (g_fast_exit) fast_exit(rc, o.verbose);   // (every thread joined, the archive closed)
-    return rc;
+};
+
+// -c: the pipeline's stages in order
+int compress(const Options& o, const cli::CliKnobs& kn)
+{
+    Pipeline p(o, kn);
+    if (!p.open_inputs()) return 1;
+    if (!p.plan.early_read && !p.create_contexts()) {
+        fprintf(stderr, "seqarc_amd: %s\n", p.ctx_err.c_str());
+        return 1;
+    }
+    p.start_reader();
+    p.start_parsers();
+    // early_read: the contexts now, beside the reader's first batch
+    if (p.plan.early_read && !p.create_contexts()) p.fail(p.ctx_err);
+    p.start_encoders();
+    p.write_blocks();
+    p.join();
+    if (!p.finish_archive()) return 1;
+    p.release_or_leave();
+    p.report();
+    if (g_fast_exit) fast_exit(p.rc, o.verbose);   // (every thread joined, the archive closed)
+    return p.rc;
 }
+
 
 // ---- decompression --------------------------------------------------------
 uint64_t be(const uint8_t* p, int n)
@@ -3407,17 +3266,10 @@ int main(int argc, char** argv)
     // default of four queues (which the GPU boxes preset), the contexts' streams
     // share queues and one context's packets wait behind another's (DESIGN.md
     // 5); set before the device is used, overriding a preset value
-    // (round 6: five per context with the streamed staging's copy stream;
-    // SA_CLI_HWQ=n: n per context, A/B)
-    {
-        const bool stream = std::getenv("SA_CLI_STREAM") && std::atoi(std::getenv("SA_CLI_STREAM")) != 0;
-        int per = stream ? 5 : 4;
-        if (const char* e = std::getenv("SA_CLI_HWQ")) per = std::max(1, std::atoi(e));
-        char q[16];
-        snprintf(q, sizeof q, "%d", std::min(32, per * o.contexts + 4));   // (per device)
-        setenv("GPU_MAX_HW_QUEUES", q, 1);
-    }
-    const int rc = compress(o);
+    // (plan_hw_queues, cli_knobs.h)
+    const cli::CliKnobs knobs = cli::parse_cli_knobs([](const char* n) -> const char* { return std::getenv(n); });
+    setenv("GPU_MAX_HW_QUEUES", std::to_string(cli::plan_hw_queues(knobs, o.contexts)).c_str(), 1);   // (per device)
+    const int rc = compress(o, knobs);
     if (o.verbose && !o.decompress)   // (a compression that released its buffers: the same stamps)
         fprintf(stderr, "seqarc_amd: monotonic clock: main %.6f, exit %.6f\n", g_main_s, mono_s());
     return rc;

@@ -217,7 +217,9 @@ def test_cli_reference_path(tmp_path):
 def test_cli_reference_shm(tmp_path):
     """-i -s / -c -s (README.md:32): the index image goes to /dev/shm/<ref file
     name> (IHashRefIndex::createShm@0x41f280) and -c -s encodes from it with no
-    ref.fa.hash on disk -- the same archive as from the file."""
+    ref.fa.hash on disk -- the same archive as from the file.  Beside it (the
+    smallest input of the reference path's CLI cases): -c --stage-ahead with the
+    reference gives the archive of the same command without it."""
     import hashlib
     import os
     import subprocess
@@ -240,6 +242,12 @@ def test_cli_reference_shm(tmp_path):
         assert open(shm, "rb").read() == (tmp_path / (name + ".hash")).read_bytes()
         r = run(base + [name, "-1", "a_1.fq", "-2", "a_2.fq", "file"])
         assert r.returncode == 0, r.stderr
+        # --stage-ahead with a reference, two contexts: the batches staged by the helper into
+        # the alternate input and run with sa_run_input_aligned at their place k in the chain
+        r = run(base + ["--stage-ahead", "--contexts", "2", "-v", name, "-1", "a_1.fq", "-2", "a_2.fq", "ahead"])
+        assert r.returncode == 0, r.stderr
+        assert r.stderr.count(b"staged ahead") >= 2, r.stderr   # (more than one batch through the chain)
+        assert (tmp_path / "ahead.arc").read_bytes() == (tmp_path / "file.arc").read_bytes()
         os.remove(tmp_path / (name + ".hash"))
         r = run(base + ["-s", "-v", name, "-1", "a_1.fq", "-2", "a_2.fq", "mem"])
         assert r.returncode == 0, r.stderr

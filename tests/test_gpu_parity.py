@@ -390,7 +390,11 @@ def test_cli_archive(tmp_path, test_pair):
 def test_cli_multi_device_gather(tmp_path, test_pair):
     """--devices: batches dealt to several encoder contexts (one host thread each)
     and gathered in input order -- the same archive as one context.  On the
-    one-GPU test box the contexts share device 0 (--share-device)."""
+    one-GPU test box the contexts share device 0 (--share-device).  Every way a
+    batch reaches the device gives that archive: whole-batch staging, the host
+    parse, the streamed uploads, --stage-ahead, and --ramp's smaller first
+    batches."""
+    import re
     import subprocess
     exe = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "fastqueeze_amd", "bin",
                        "seqarc_amd")
@@ -418,9 +422,25 @@ def test_cli_multi_device_gather(tmp_path, test_pair):
     env7 = dict(os.environ, SA_CLI_SEG_SLICES="1", SA_CLI_STREAM="1")
     r7 = subprocess.run(base[:-1] + ["3", "--contexts", "2", "-o", str(tmp_path / "seven")],
                         capture_output=True, text=True, timeout=120, env=env7)
+    # --stage-ahead (each context's helper stages the next batch into the alternate input with a
+    # staging context); with --ramp and C * B = 2 below the block estimate the ramp survives, so
+    # the staging contexts take sa_set_reserve too; and --ramp on the default path
+    r8 = subprocess.run(base[:-1] + ["2", "--contexts", "2", "--stage-ahead", "-o", str(tmp_path / "eight")],
+                        capture_output=True, text=True, timeout=120)
+    r9 = subprocess.run(base + ["--contexts", "2", "--stage-ahead", "--ramp", "-v", "-o", str(tmp_path / "nine")],
+                        capture_output=True, text=True, timeout=120)
+    r10 = subprocess.run(base[:-1] + ["2", "--contexts", "2", "--ramp", "-v", "-o", str(tmp_path / "ten")],
+                         capture_output=True, text=True, timeout=120)
     assert r1.returncode == 0 and r3.returncode == 0 and r4.returncode == 0, (r1.stderr, r3.stderr, r4.stderr)
     assert r5.returncode == 0 and r6.returncode == 0 and r7.returncode == 0, (r5.stderr, r6.stderr, r7.stderr)
+    assert r8.returncode == 0 and r9.returncode == 0 and r10.returncode == 0, (r8.stderr, r9.stderr, r10.stderr)
     one = open(tmp_path / "one.arc", "rb").read()
+    assert one == open(tmp_path / "eight.arc", "rb").read() == open(tmp_path / "nine.arc", "rb").read()
+    assert one == open(tmp_path / "ten.arc", "rb").read()
+    assert "staged ahead" in r9.stderr
+    # the ramp's first batch of each context is smaller than B = 2: one block each, then two
+    sizes = dict(re.findall(r"batch (\d+) \((\d+) blocks\)", r10.stderr))
+    assert sizes["0"] == sizes["1"] == "1" and sizes["2"] == "2", r10.stderr
     assert one == open(tmp_path / "three.arc", "rb").read() == open(tmp_path / "four.arc", "rb").read()
     assert one == open(tmp_path / "five.arc", "rb").read()
     assert one == open(tmp_path / "six.arc", "rb").read() == open(tmp_path / "seven.arc", "rb").read()
