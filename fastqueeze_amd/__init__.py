@@ -22,7 +22,8 @@ import numpy as np
 from . import build as _build
 
 __all__ = ["SeqArcError", "blocks_from_fastq", "Block", "Config", "Encoder", "cut_se", "cut_pe", "parse_se", "parse_pe", "analyze_ids",
-           "load_library", "BLOCK_SIZE", "Input", "bgzf_scan", "Inflater", "BGZF_MEMBER", "INFLATE_STATUS"]
+           "load_library", "BLOCK_SIZE", "Input", "bgzf_scan", "Inflater", "BGZF_MEMBER", "INFLATE_STATUS",
+           "Gunzipper", "GunzipState", "GunzipInfo"]
 
 BLOCK_SIZE = 50 << 20   # SeqArcParam BlockSize(M) = 50 (ctor @0x40776f)
 
@@ -153,6 +154,10 @@ def load_library(path: str | None = None):
         "sa_inflate_members": ([P, P, U64, P, C.c_uint32, P, U64, P], I32),
         "sa_inflater_error": ([P], C.c_char_p), "sa_inflater_kernel_ms": ([P], C.c_float),
         "sa_inflater_grid": ([P], C.c_uint32),
+        "sa_gunzipper_create": ([I32], P), "sa_gunzipper_destroy": ([P], None),
+        "sa_gunzip_run": ([P, P, U64, I32, P, P, U64, P, P, P], I32),
+        "sa_gunzipper_error": ([P], C.c_char_p), "sa_gunzipper_kernel_ms": ([P], C.c_float),
+        "sa_gunzipper_grid": ([P], C.c_uint32), "sa_gunzipper_chunk": ([P], C.c_uint32),
     }
     for name, (args, res) in sigs.items():
         fn = getattr(lib, name)
@@ -548,7 +553,7 @@ class HostBuffer:
 BGZF_MEMBER = np.dtype([("in_off", "<u8"), ("in_len", "<u4"), ("out_off", "<u8"), ("isize", "<u4"), ("crc", "<u4")],
                        align=True)
 INFLATE_STATUS = {0: "ok", 1: "input overrun", 2: "bad block type or stored length", 3: "bad code lengths",
-                  4: "distance too far", 5: "output size is not ISIZE", 6: "CRC mismatch"}
+                  4: "distance too far", 5: "output size is not ISIZE", 6: "CRC mismatch", 7: "not a gzip member header"}
 
 
 def bgzf_scan(data, max_members: int | None = None):
@@ -630,6 +635,107 @@ class Inflater:
             raise SeqArcError(f"BGZF member {i} failed to inflate: status {int(status[i])} "
                               f"({INFLATE_STATUS.get(int(status[i]), '?')})")
         return out
+
+
+class GunzipState(C.Structure):
+    """sa_gunzip_state: where a gzip stream stands between two sa_gunzip_run calls (zeros: a file's start)."""
+    _fields_ = [("in_stream", C.c_uint32), ("bit", C.c_uint32), ("win_len", C.c_uint32), ("crc", C.c_uint32),
+                ("len", C.c_uint64), ("ended", C.c_uint32), ("reserved", C.c_uint32), ("window", C.c_uint8 * 32768)]
+
+
+class GunzipInfo(C.Structure):
+    """sa_gunzip_info: what one sa_gunzip_run call did."""
+    _fields_ = [("chunks", C.c_uint32), ("candidates", C.c_uint32), ("waves_confirmed", C.c_uint32),
+                ("false_skipped", C.c_uint32), ("members_ended", C.c_uint32), ("end_wave", C.c_uint32),
+                ("end_why", C.c_uint32), ("status", C.c_uint32), ("find_ms", C.c_float), ("spec_ms", C.c_float),
+                ("chain_ms", C.c_float), ("resolve_ms", C.c_float), ("crc_ms", C.c_float)]
+
+    def as_dict(self) -> dict:
+        return {n: getattr(self, n) for n, _ in self._fields_}
+
+
+class Gunzipper:
+    """Ordinary gzip (gzip, pigz, concatenated members) inflated on the device by
+    speculation (sa_gunzipper_*): a wave per chunk of compressed bytes, the
+    members' CRC-32 and ISIZE checked.  Its device slabs grow on demand and are kept."""
+
+    SLAB = 32 << 20   # compressed bytes fed per call
+
+    def __init__(self, device: int = 0):
+        self._lib = load_library()
+        self._h = self._lib.sa_gunzipper_create(device)
+        if not self._h:
+            raise SeqArcError(f"sa_gunzipper_create failed: no usable gfx950 device {device}")
+        self.last_info: dict = {}
+        self.calls: list[dict] = []   # the info of every call of the last gunzip()
+
+    def close(self):
+        if self._h:
+            self._lib.sa_gunzipper_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    @property
+    def last_kernel_ms(self) -> float:
+        return float(self._lib.sa_gunzipper_kernel_ms(self._h))
+
+    @property
+    def grid(self) -> int:
+        """(tests and diagnostics) Workgroups a launch uses at most (SA_GUNZIP_GRID)."""
+        return int(self._lib.sa_gunzipper_grid(self._h))
+
+    @property
+    def chunk(self) -> int:
+        """Compressed bytes per chunk (SA_GUNZIP_CHUNK)."""
+        return int(self._lib.sa_gunzipper_chunk(self._h))
+
+    def run(self, data, state: GunzipState, out: np.ndarray, eof: bool = True, out_cap: int | None = None):
+        """One sa_gunzip_run into the uint8 array `out`: (return value, out_bytes, in_used);
+        `state` is updated and .last_info set.  A negative return value raises."""
+        a = _as_u8(data)
+        ob, used, info = C.c_uint64(0), C.c_uint64(0), GunzipInfo()
+        rc = self._lib.sa_gunzip_run(self._h, _ptr(a), a.size, int(eof), C.byref(state), _ptr(out),
+                                     out.size if out_cap is None else out_cap, C.byref(ob), C.byref(used), C.byref(info))
+        self.last_info = info.as_dict()
+        if rc < 0:
+            raise SeqArcError(f"sa_gunzip_run ({rc}): {self._lib.sa_gunzipper_error(self._h).decode()}")
+        return rc, ob.value, used.value
+
+    def gunzip(self, data, slab: int | None = None, out_cap: int | None = None) -> bytes:
+        """A whole gzip file's text: sa_gunzip_run over slabs of `slab` compressed
+        bytes, what a call leaves unconsumed carried into the next.  Raises on a
+        corrupt stream, and where the device path would hand the stream to the
+        host (a call of two chunks or more that confirms less than one)."""
+        a = _as_u8(data)
+        slab = slab or self.SLAB
+        cap = out_cap or max(64 << 20, 16 * slab)
+        out = np.empty(cap, np.uint8)
+        state = GunzipState()
+        parts, at, carry = [], 0, np.zeros(0, np.uint8)
+        self.calls = []
+        while True:
+            take = min(slab, a.size - at)
+            buf = np.concatenate([carry, a[at:at + take]]) if carry.size else a[at:at + take]
+            at += take
+            eof = at == a.size
+            rc, ob, used = self.run(buf, state, out, eof)
+            self.calls.append(self.last_info)
+            parts.append(out[:ob].tobytes())
+            if rc > 0:
+                raise SeqArcError(f"gzip stream is corrupt: status {rc} ({INFLATE_STATUS.get(rc, '?')}) after "
+                                  f"{sum(map(len, parts))} text bytes")
+            carry = buf[used:]
+            if state.ended or (eof and carry.size == 0):
+                break
+            if (self.last_info["chunks"] >= 2 and used < self.chunk) or (eof and not used and not ob):
+                raise SeqArcError(f"the device path makes too little progress (end_why {self.last_info['end_why']}): "
+                                  "inflate this stream on the host")
+        return b"".join(parts)
 
 
 class Input:

@@ -2140,6 +2140,7 @@ int sa_encode_blocks(sa_ctx* ctx, const sa_block* in, int n, const sa_cfg* cfg, 
 // FASTQ text parsed on the device (sa_stage_text)
 #include "sa_parse.hip"
 #include "sa_inflate.hip"
+#include "sa_gunzip.hip"
 
 // the HASH reference-index path
 #include "sa_hash.hip"

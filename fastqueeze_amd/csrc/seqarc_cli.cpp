@@ -27,6 +27,8 @@
 //                    consumers (no device); --ingest-crc: the consumers CRC the texts
 //   --gpu-inflate    BGZF inputs are inflated on the first device (sa_inflate_members)
 //                    instead of on host threads; other gzip files keep the host path
+//   --gpu-gunzip     gzip inputs that are not BGZF (gzip, pigz, concatenated members) are
+//                    inflated on the first device by speculation (sa_gunzip_run)
 //
 // Compression mirrors SeqArc-1.6 main@0x41fd40 -> SeqArcContext::doReadAndEncode
 // @0x41a4e0 as a stream: one reader thread cuts 50 MiB blocks as the input
@@ -82,11 +84,13 @@ int usage()
             "                  [--slevel K] [--qlevel Q] [--devices N] [--contexts K] [--batch BLOCKS]\n"
             "                  [--block-size MiB] [--device D] [--share-device] [--ramp] [--release]\n"
             "                  [--stage-ahead] [--writers N] [--read-threads N] [--gpu-inflate]\n"
+            "                  [--gpu-gunzip]\n"
             "       seqarc_amd -d [-t N] [-f] [-p] [-P 1|2|3] [ref.fa] ARCHIVE.arc [PREFIX] [-o PREFIX]\n"
             "       seqarc_amd -i ref.fa            (HASH index: ref.fa.hash + ref.fa.md5)\n"
             "       (-s with -i / -c / -d and ref.fa: the index image in /dev/shm/<ref file name>)\n"
             "       (-c / -d with ref.fa: the reference path; -I N insert size, --maxmis M)\n"
-            "       (--gpu-inflate: BGZF inputs of -c are inflated on the first device, not on host threads)\n");
+            "       (--gpu-inflate: BGZF inputs of -c are inflated on the first device, not on host threads)\n"
+            "       (--gpu-gunzip: gzip inputs of -c that are not BGZF are inflated on the first device)\n");
     return 2;
 }
 
@@ -362,6 +366,7 @@ struct GzStream {
     static constexpr size_t kMaxQueued = 512u << 20;
 
     int gpu_device = -1;   // >= 0 (--gpu-inflate): BGZF members are inflated on this device
+    int gunzip_device = -1;   // >= 0 (--gpu-gunzip): gzip that is not BGZF is inflated on this device
     bool verbose = false;
     std::string name;
 
@@ -375,9 +380,9 @@ struct GzStream {
                h[12] == 'B' && h[13] == 'C' && h[14] == 2 && h[15] == 0;
         prod = std::thread([this]() {
             lower_priority();
-            if (gpu_device >= 0 && !bgzf && verbose)
+            if (gpu_device >= 0 && !bgzf && gunzip_device < 0 && verbose)
                 fprintf(stderr, "seqarc_amd: --gpu-inflate: %s is gzip but not BGZF, inflating it on the host\n", name.c_str());
-            const bool ok = bgzf ? (gpu_device >= 0 ? run_bgzf_gpu() : run_bgzf()) : run_plain();
+            const bool ok = bgzf ? (gpu_device >= 0 ? run_bgzf_gpu() : run_bgzf()) : gunzip_device >= 0 ? run_plain_gpu() : run_plain();
             std::lock_guard<std::mutex> g(mu);
             failed = !ok;
             done = true;
@@ -409,12 +414,13 @@ struct GzStream {
         return (long)got;
     }
     // one member or several concatenated (gzread's reading of them)
-    bool run_plain()
+    // (at0: the file offset of the first member -- run_host_from continues a file there)
+    bool run_plain(uint64_t at0 = 0)
     {
         z_stream z{};
         if (inflateInit2(&z, 15 + 16) != Z_OK) return false;
         std::vector<uint8_t> in(4u << 20);
-        uint64_t at = 0;
+        uint64_t at = at0;
         bool eof = false, member_end = false;
         Bytes out(8u << 20);
         size_t have = 0;
@@ -873,6 +879,361 @@ struct GzStream {
         }
         return finish(true);
     }
+    // The rest of a gzip file on the host, from where sa_gunzip_run left it: inside
+    // a deflate stream a raw inflate with the state's window as its dictionary,
+    // primed with the bits left of the current byte, the member's running CRC-32
+    // and length carried on and compared with the trailer here; the members after
+    // it through run_plain.
+    bool run_host_from(const sa_gunzip_state& gs, uint64_t at)
+    {
+        if (gs.ended) return true;
+        if (gs.in_stream) {
+            z_stream z{};
+            if (inflateInit2(&z, -15) != Z_OK) return false;
+            auto fail = [&]() {
+                inflateEnd(&z);
+                return false;
+            };
+            if (gs.win_len && inflateSetDictionary(&z, gs.window + (32768 - gs.win_len), gs.win_len) != Z_OK) return fail();
+            std::vector<uint8_t> in(4u << 20);
+            Bytes out(8u << 20);
+            size_t have = 0;
+            uint32_t crc = gs.crc;
+            uint64_t len = gs.len;
+            bool eof = false, first = true, end = false;
+            while (!end) {
+                if (z.avail_in == 0) {
+                    const long r = eof ? 0 : readn(in.data(), in.size(), at);
+                    if (r <= 0) return fail();   // a read error, or the file ends inside the member
+                    z.next_in = in.data();
+                    z.avail_in = (uInt)r;
+                    if (first && gs.bit) {
+                        if (inflatePrime(&z, 8 - (int)gs.bit, in[0] >> gs.bit) != Z_OK) return fail();
+                        z.next_in++;
+                        z.avail_in--;
+                    }
+                    first = false;
+                }
+                z.next_out = out.data() + have;
+                z.avail_out = (uInt)(out.size() - have);
+                const int rc = inflate(&z, Z_NO_FLUSH);
+                const size_t now_have = out.size() - z.avail_out;
+                crc = (uint32_t)crc32(crc, out.data() + have, (uInt)(now_have - have));
+                len += now_have - have;
+                have = now_have;
+                if (rc == Z_STREAM_END) end = true;
+                else if (rc != Z_OK && rc != Z_BUF_ERROR) return fail();
+                if (have == out.size() || end) {
+                    out.resize(have);
+                    if (have && !push(std::move(out))) {
+                        inflateEnd(&z);
+                        return true;
+                    }
+                    out = Bytes();
+                    out.resize(8u << 20);
+                    have = 0;
+                }
+            }
+            // the trailer: what inflate left of the slab, then the file
+            uint8_t t[8];
+            size_t k = std::min<size_t>(8, z.avail_in);
+            memcpy(t, z.next_in, k);
+            at -= z.avail_in - k;   // (readn moved `at` past the slab)
+            inflateEnd(&z);
+            if (k < 8 && readn(t + k, 8 - k, at) != (long)(8 - k)) return false;
+            const uint32_t tcrc = t[0] | t[1] << 8 | t[2] << 16 | (uint32_t)t[3] << 24;
+            const uint32_t tlen = t[4] | t[5] << 8 | t[6] << 16 | (uint32_t)t[7] << 24;
+            if (tcrc != crc || tlen != (uint32_t)len) return false;
+        }
+        // the next member, if it is one (trailing bytes otherwise end the stream)
+        uint8_t m[2];
+        uint64_t peek = at;
+        if (readn(m, 2, peek) != 2 || m[0] != 0x1f || m[1] != 0x8b) return true;
+        return run_plain(at);
+    }
+    // Gzip that is not BGZF with --gpu-gunzip: run_bgzf_gpu's shape around
+    // sa_gunzip_run.  This thread reads the file into recycled page-locked slabs,
+    // up to kInFlight ahead, each with room in front; the device thread puts what
+    // the last call left unconsumed (the unconfirmed tail of its slab) into that
+    // room and inflates carry + slab into one of two page-locked output slabs,
+    // from which the copier thread copies the text into the queue's chunk while
+    // the next call fills the other.  A call of two chunks or more that confirms
+    // less than one chunk of compressed bytes (stored-only files, runs of enormous
+    // ratio, many tiny members: one wave does all the work), or leaves more than
+    // the room holds, ends the device path: the host continues from the state
+    // (run_host_from).
+    bool run_plain_gpu()
+    {
+        const size_t kSlab = 32u << 20;
+        const size_t kRoom = 8u << 20;   // in front of a slab: the carry
+        const size_t kInFlight = 4;
+        const uint64_t kOutCap = 512ull << 20;
+        struct Slab {
+            uint8_t* in = nullptr;   // sa_host_alloc, kRoom + kSlab bytes
+            size_t have = 0;
+            uint64_t file_at = 0;
+            bool last = false;
+        };
+        auto now = []() { return std::chrono::steady_clock::now(); };
+        auto ms_since = [&](std::chrono::steady_clock::time_point t) {
+            return std::chrono::duration<double, std::milli>(now() - t).count();
+        };
+        const auto t_begin = now();
+        sa_gunzipper* gz = sa_gunzipper_create(gunzip_device);
+        const double create_ms = ms_since(t_begin);
+        if (!gz) {
+            fprintf(stderr, "seqarc_amd: --gpu-gunzip: no usable gfx950 device %d\n", gunzip_device);
+            return false;
+        }
+        const uint64_t chunk = sa_gunzipper_chunk(gz);
+        std::mutex pm;
+        std::condition_variable pcv;
+        std::deque<std::unique_ptr<Slab>> jobs;   // in file order
+        std::vector<uint8_t*> free_in;
+        bool quit = false, bad = false, stopped = false, takeover = false;
+        std::unique_ptr<sa_gunzip_state> gs(new sa_gunzip_state());
+        uint64_t host_at = 0;   // takeover: the file offset the host continues at
+        double kernel_ms[5] = {}, call_ms = 0, copy_ms = 0, push_ms = 0, alloc_ms = 0, idle_ms = 0, in_alloc_ms = 0, out_wait_ms = 0;
+        uint64_t n_calls = 0, n_chunks = 0, n_cand = 0, n_conf = 0, n_false = 0, n_members = 0, text_bytes = 0;
+        std::thread gpu([&]() {
+            lower_priority();
+            struct Out {
+                uint8_t* p = nullptr;
+                uint64_t cap = 0, bytes = 0;
+                bool busy = false;   // handed to the copier
+            } outs[2];
+            std::mutex cm;
+            std::condition_variable ccv;
+            std::deque<int> handed;   // output slabs to copy, in order
+            bool cquit = false, cgone = false;
+            std::thread copier([&]() {
+                lower_priority();
+                for (;;) {
+                    int k;
+                    {
+                        std::unique_lock<std::mutex> lk(cm);
+                        ccv.wait(lk, [&] { return cquit || !handed.empty(); });
+                        if (handed.empty()) break;
+                        k = handed.front();
+                    }
+                    bool ok = true;
+                    if (!cgone) {   // (only this thread writes cgone)
+                        auto t0 = now();
+                        Bytes chunk_out(outs[k].bytes);
+                        memcpy(chunk_out.data(), outs[k].p, outs[k].bytes);
+                        copy_ms += ms_since(t0);
+                        t0 = now();
+                        ok = push(std::move(chunk_out));
+                        push_ms += ms_since(t0);   // (the queue is full: the block cut is behind)
+                    }
+                    std::lock_guard<std::mutex> g(cm);
+                    if (!ok) cgone = true;
+                    handed.pop_front();
+                    outs[k].busy = false;
+                    ccv.notify_all();
+                }
+            });
+            int turn = 0;
+            std::vector<uint8_t> carry;   // what the last call left of its input
+            bool fail = false, gone = false, leave = false, over = false;
+            while (!fail && !gone && !leave && !over) {
+                std::unique_ptr<Slab> s;
+                {
+                    const auto t0 = now();
+                    std::unique_lock<std::mutex> lk(pm);
+                    pcv.wait(lk, [&] { return quit || !jobs.empty(); });
+                    idle_ms += ms_since(t0);   // (waiting for the reader's next slab)
+                    if (jobs.empty()) break;
+                    s = std::move(jobs.front());   // (it leaves the queue when it is done: the reader counts it in flight)
+                }
+                // carry + slab, contiguous; then again with what is left, until a call needs the next slab
+                uint8_t* in = s->in + kRoom - carry.size();
+                size_t n = carry.size() + s->have;
+                uint64_t in_at = s->file_at - carry.size();   // the file offset of in[0]
+                if (!carry.empty()) memcpy(in, carry.data(), carry.size());
+                carry.clear();
+                for (;;) {
+                    Out& o = outs[turn];
+                    turn ^= 1;
+                    {
+                        const auto t0 = now();
+                        std::unique_lock<std::mutex> lk(cm);
+                        ccv.wait(lk, [&] { return !o.busy; });
+                        out_wait_ms += ms_since(t0);   // (the copier still holds this slab)
+                        if (cgone) {
+                            gone = true;
+                            break;
+                        }
+                    }
+                    const uint64_t want = std::min<uint64_t>(kOutCap, 6ull * n + (64u << 20));
+                    if (want > o.cap) {
+                        const auto t0 = now();
+                        if (o.p) sa_host_free(o.p);
+                        o.cap = want;
+                        o.p = static_cast<uint8_t*>(sa_host_alloc(o.cap));
+                        if (!o.p) {
+                            fprintf(stderr, "seqarc_amd: --gpu-gunzip: cannot allocate %llu bytes of host memory\n",
+                                    (unsigned long long)o.cap);
+                            o.cap = 0;
+                            fail = true;
+                            break;
+                        }
+                        alloc_ms += ms_since(t0);
+                    }
+                    const auto t0 = now();
+                    uint64_t out_bytes = 0, in_used = 0;
+                    sa_gunzip_info info{};
+                    const int rc = sa_gunzip_run(gz, in, n, s->last ? 1 : 0, gs.get(), o.p, o.cap, &out_bytes, &in_used, &info);
+                    if (rc < 0) fprintf(stderr, "seqarc_amd: --gpu-gunzip: %s\n", sa_gunzipper_error(gz));
+                    if (rc > 0)
+                        fprintf(stderr, "seqarc_amd: --gpu-gunzip: %s: the gzip stream is corrupt (status %d near byte %llu)\n",
+                                name.c_str(), rc, (unsigned long long)(in_at + in_used));
+                    if (rc != 0) {   // (> 0: the host path's error)
+                        fail = true;
+                        break;
+                    }
+                    call_ms += ms_since(t0);
+                    const float k[5] = {info.find_ms, info.spec_ms, info.chain_ms, info.resolve_ms, info.crc_ms};
+                    for (int i = 0; i < 5; i++) kernel_ms[i] += k[i];
+                    n_calls++;
+                    n_chunks += info.chunks;
+                    n_cand += info.candidates;
+                    n_conf += info.waves_confirmed;
+                    n_false += info.false_skipped;
+                    n_members += info.members_ended;
+                    text_bytes += out_bytes;
+                    if (out_bytes) {
+                        std::lock_guard<std::mutex> g(cm);
+                        o.bytes = out_bytes;
+                        o.busy = true;
+                        handed.push_back((int)(&o - outs));
+                        ccv.notify_all();
+                    }
+                    in += in_used;
+                    n -= in_used;
+                    in_at += in_used;
+                    if (gs->ended || (s->last && n == 0)) {
+                        over = true;
+                        break;
+                    }
+                    // (one wave confirmed in a call of four chunks or more: the stream has no block starts
+                    // to find -- stored or fixed blocks only -- and one wave would go on doing all the work)
+                    const bool low = (info.chunks >= 2 && in_used < chunk) || (s->last && !in_used && !out_bytes) ||
+                                     (info.chunks >= 4 && info.waves_confirmed == 1 && info.end_why != SA_GZ_OUTCAP);
+                    if (low || (!s->last && n > kRoom)) {
+                        leave = true;
+                        host_at = in_at;
+                        if (verbose)
+                            fprintf(stderr,
+                                    "seqarc_amd: --gpu-gunzip: %s: a call of %u chunk(s) confirmed %llu compressed bytes (wave %u "
+                                    "ended it: %u); the host takes over at byte %llu\n",
+                                    name.c_str(), info.chunks, (unsigned long long)in_used, info.end_wave, info.end_why,
+                                    (unsigned long long)host_at);
+                        break;
+                    }
+                    // the next slab goes behind what is left, unless this is the last: then what is left runs alone
+                    if (!s->last && (info.end_why != SA_GZ_OUTCAP && info.end_why != SA_GZ_BREAKS && info.end_why != SA_GZ_FULL)) break;
+                    if (!s->last && n < chunk) break;
+                }
+                if (!fail && !gone && !leave && !over) carry.assign(in, in + n);
+                std::lock_guard<std::mutex> g(pm);
+                free_in.push_back(s->in);
+                jobs.pop_front();
+                if (fail) bad = true;
+                if (gone || over) stopped = true;
+                if (leave) takeover = true;
+                pcv.notify_all();
+            }
+            {
+                std::lock_guard<std::mutex> g(cm);
+                cquit = true;
+            }
+            ccv.notify_all();
+            copier.join();   // (it copies what was handed to it first)
+            if (cgone) {
+                std::lock_guard<std::mutex> g(pm);
+                stopped = true;
+                takeover = false;
+                pcv.notify_all();
+            }
+            for (Out& o : outs)
+                if (o.p) sa_host_free(o.p);
+        });
+        auto finish = [&](bool rc) {
+            {
+                std::lock_guard<std::mutex> g(pm);
+                quit = true;
+            }
+            pcv.notify_all();
+            gpu.join();   // (it drains the queue unless a call failed, the path left or the reader went away)
+            {
+                std::lock_guard<std::mutex> g(pm);
+                for (auto& j : jobs) free_in.push_back(j->in);
+                jobs.clear();
+                rc = rc && !bad;
+            }
+            for (uint8_t* p : free_in) sa_host_free(p);
+            if (verbose)
+                fprintf(stderr,
+                        "seqarc_amd: --gpu-gunzip: %s: %llu call(s), %llu chunk(s), %llu candidate(s), %llu wave(s) confirmed, %llu false "
+                        "candidate(s) skipped, %llu member(s), %llu text bytes on device %d in %.1f ms: gunzipper create %.1f ms, slab "
+                        "alloc %.1f + %.1f ms, sa_gunzip_run %.1f ms (gunzip kernels: find %.1f, spec %.1f, chain %.1f, resolve %.1f, "
+                        "crc %.1f ms), host copy %.1f ms beside them (the device thread waited %.1f ms for it), queue wait %.1f ms, "
+                        "waiting for slabs %.1f ms%s\n",
+                        name.c_str(), (unsigned long long)n_calls, (unsigned long long)n_chunks, (unsigned long long)n_cand,
+                        (unsigned long long)n_conf, (unsigned long long)n_false, (unsigned long long)n_members,
+                        (unsigned long long)text_bytes, gunzip_device, ms_since(t_begin), create_ms, in_alloc_ms, alloc_ms, call_ms,
+                        kernel_ms[0], kernel_ms[1], kernel_ms[2], kernel_ms[3], kernel_ms[4], copy_ms, out_wait_ms, push_ms, idle_ms,
+                        takeover ? "; the host inflated the rest" : "");
+            sa_gunzipper_destroy(gz);
+            if (rc && takeover) rc = run_host_from(*gs, host_at);
+            return rc;
+        };
+        uint64_t at = 0;
+        bool eof = false;
+        while (!eof) {
+            std::unique_ptr<Slab> s(new Slab());
+            {
+                // a slab's buffer: a recycled one, a new one while fewer than kInFlight + 1 exist
+                std::unique_lock<std::mutex> lk(pm);
+                pcv.wait(lk, [&] { return bad || stopped || takeover || jobs.size() < kInFlight; });
+                if (bad) { lk.unlock(); return finish(false); }
+                if (stopped || takeover) { lk.unlock(); return finish(true); }
+                if (!free_in.empty()) {
+                    s->in = free_in.back();
+                    free_in.pop_back();
+                }
+            }
+            if (!s->in) {
+                const auto t0 = now();
+                s->in = static_cast<uint8_t*>(sa_host_alloc(kRoom + kSlab));
+                in_alloc_ms += ms_since(t0);
+            }
+            if (!s->in) return finish(false);
+            s->file_at = at;
+            const long r = readn(s->in + kRoom, kSlab, at);
+            if (r < 0) {
+                {
+                    std::lock_guard<std::mutex> g(pm);
+                    free_in.push_back(s->in);
+                }
+                return finish(false);
+            }
+            if ((size_t)r < kSlab) eof = true;
+            s->have = (size_t)r;
+            s->last = eof;
+            {
+                std::lock_guard<std::mutex> g(pm);
+                jobs.push_back(std::move(s));
+            }
+            pcv.notify_all();
+        }
+        {
+            std::unique_lock<std::mutex> lk(pm);
+            pcv.wait(lk, [&] { return bad || stopped || takeover || jobs.empty(); });
+        }
+        return finish(true);
+    }
     // up to n bytes into dst; 0 at the end; -1 on a gzip error
     long read(uint8_t* dst, size_t n)
     {
@@ -915,6 +1276,7 @@ struct GzStream {
 // parallel).
 int g_gz_workers = 8;   // inflate threads per BGZF input (-t / 2 for PE)
 int g_gpu_inflate_dev = -1;   // --gpu-inflate: the device that inflates BGZF inputs
+int g_gpu_gunzip_dev = -1;    // --gpu-gunzip: the device that inflates gzip inputs that are not BGZF
 bool g_gz_verbose = false;
 
 struct Input {
@@ -931,6 +1293,7 @@ struct Input {
         if (is_gz) {
             gz.reset(new GzStream());
             gz->gpu_device = g_gpu_inflate_dev;
+            gz->gunzip_device = g_gpu_gunzip_dev;
             gz->verbose = g_gz_verbose;
             gz->name = path;
             gz->start(fd, g_gz_workers);
@@ -1654,7 +2017,7 @@ bool parse_job(Job& j, bool pe, ParsedPool& pool, TextPool& texts, bool keep_tex
 struct Options : cli::PlanOpts {   // (PlanOpts, cli_plan.h: the options the batch plan reads)
     const char *f1 = nullptr, *f2 = nullptr, *out = nullptr, *arc = nullptr, *ref = nullptr;
     bool compress = false, decompress = false, index = false, force = false, in_dir = false, share_device = false,
-         verbose = false, release = false, shm = false, maxmis_set = false, ingest_crc = false, gpu_inflate = false;
+         verbose = false, release = false, shm = false, maxmis_set = false, ingest_crc = false, gpu_inflate = false, gpu_gunzip = false;
     int writers = 8;        // --writers: the archive writer's copy threads (ArcWriter; 1: write(2) in order)
     int pipe = 0, device = 0, block_mib = 50, maxmis = 7;
     int insert = 0;
@@ -2089,6 +2452,7 @@ struct Pipeline {
         // inflate threads per BGZF input: the -t share (the device parse leaves the host threads free)
         g_gz_workers = std::max(2, (o.threads > 0 ? o.threads : 16) / (pe ? 2 : 1));
         g_gpu_inflate_dev = o.gpu_inflate ? o.device : -1;
+        g_gpu_gunzip_dev = o.gpu_gunzip ? o.device : -1;
         g_gz_verbose = o.verbose;
         struct stat sb;
         for (const char* f : {o.f1, pe ? o.f2 : nullptr}) {
@@ -3211,6 +3575,7 @@ int main(int argc, char** argv)
         else if (!strcmp(a, "--ingest-only")) o.ingest_only = true;
         else if (!strcmp(a, "--ingest-crc")) o.ingest_crc = true;
         else if (!strcmp(a, "--gpu-inflate")) o.gpu_inflate = true;
+        else if (!strcmp(a, "--gpu-gunzip")) o.gpu_gunzip = true;
         else if (!strcmp(a, "--read-threads")) { if (!ival(o.read_threads, 0)) return usage(); }
         else if (!strcmp(a, "--writers")) { if (!ival(o.writers, 1)) return usage(); }
         else if (!strcmp(a, "--no-ramp")) o.ramp = false;

@@ -457,6 +457,69 @@ float sa_inflater_kernel_ms(const sa_inflater *);      /* HIP events around the 
  * sa_inflater_create; lets a test assert that the knob took effect */
 uint32_t sa_inflater_grid(const sa_inflater *);
 
+/* ---- ordinary gzip inflated on the device -----------------------------------
+ * A gzip member (gzip, pigz, members concatenated) carries no sizes and no restart points.
+ * sa_gunzip_run inflates it by speculation: the compressed bytes are cut into chunks
+ * (env SA_GUNZIP_CHUNK, bytes), k_gz_find looks in each for the first bit position at which
+ * a dynamic block can start, k_gz_spec decodes one wave per start into 16-bit symbols in
+ * which references to the unknown 32 KiB before the start are markers, k_gz_chain confirms
+ * the starts a predecessor's decode ended at exactly and derives every confirmed wave's true
+ * window, k_gz_resolve replaces the markers and k_gz_crc sums the text; the host compares
+ * each member's CRC-32 and ISIZE with its trailer.  No kernel waits for another wave. */
+enum {
+    SA_INFL_HEADER = 7,  /* the stream does not begin with a gzip member header            */
+    /* why the confirmed prefix of a call ended (sa_gunzip_info.end_why), besides SA_INFL_* */
+    SA_GZ_MET = 16,      /* (a wave's stop: a block boundary at the next start)             */
+    SA_GZ_FULL = 17,     /* the wave's symbol range is full (env SA_GUNZIP_RATIO)           */
+    SA_GZ_END = 18,      /* the input ends after a member's trailer, or no member follows   */
+    SA_GZ_BREAKS = 19,   /* the wave ended eight members                                    */
+    SA_GZ_OUTCAP = 20    /* the next wave's text does not fit out_cap                       */
+};
+/* Where a stream stands between calls.  All zeros: the start of a file. */
+typedef struct {
+    uint32_t in_stream;      /* 0: a member header is next; 1: inside a deflate stream, at a block start */
+    uint32_t bit;            /* in_stream: bits of the next call's first byte that are consumed (0..7)   */
+    uint32_t win_len;        /* in_stream: text bytes of this member before the position, at most 32768  */
+    uint32_t crc;            /* CRC-32 of the current member's text so far                               */
+    uint64_t len;            /* ... and its length                                                       */
+    uint32_t ended;          /* 1: the stream is over (bytes that are no gzip member follow the last)    */
+    uint32_t reserved;
+    uint8_t window[32768];   /* the last win_len text bytes, at the END of the array (a dictionary)      */
+} sa_gunzip_state;
+typedef struct {
+    uint32_t chunks;            /* chunks of the call's input                                */
+    uint32_t candidates;        /* block starts the finder returned                          */
+    uint32_t waves_confirmed;   /* waves whose text is in the output                         */
+    uint32_t false_skipped;     /* candidates the confirmed waves decoded past               */
+    uint32_t members_ended;     /* trailers checked                                          */
+    uint32_t end_wave;          /* the wave that ended the confirmed prefix ...              */
+    uint32_t end_why;           /* ... and why: SA_GZ_* or SA_INFL_*                         */
+    uint32_t status;            /* the return value when it is > 0                           */
+    float find_ms, spec_ms, chain_ms, resolve_ms, crc_ms;   /* HIP events around each kernel */
+} sa_gunzip_info;
+typedef struct sa_gunzipper sa_gunzipper;
+sa_gunzipper *sa_gunzipper_create(int device);        /* own stream and device slabs; no sa_ctx needed */
+void sa_gunzipper_destroy(sa_gunzipper *);
+/* Inflates in[0..in_bytes) (at most 256 MiB), which continues the stream at *state, as far as
+ * the confirmed prefix reaches and its text fits out_cap (cut at a wave's boundary), into
+ * out[0..*out_bytes); *in_used: the whole input bytes consumed -- the caller carries
+ * in[*in_used..) into the next call, in front of new input; *state is updated.  eof: no input
+ * follows in[0..in_bytes).  info may be NULL.  The copies are DMAs when in / out are
+ * sa_host_alloc memory and work from pageable memory too.
+ * 0: progress, a clean end of the stream (state->ended, or eof with *in_used == in_bytes and
+ * no member open), or no progress because the input ends inside the first block (more input
+ * decides) or the first wave's symbols do not fit (info->end_why == SA_GZ_FULL: the caller
+ * continues on the host from *state); >0: the stream is corrupt, an SA_INFL_* code (the text
+ * before the error is delivered); <0: call error (-2: out_cap is too small for the first wave) */
+int sa_gunzip_run(sa_gunzipper *, const uint8_t *in, uint64_t in_bytes, int eof, sa_gunzip_state *state,
+                  uint8_t *out, uint64_t out_cap, uint64_t *out_bytes, uint64_t *in_used, sa_gunzip_info *info);
+const char *sa_gunzipper_error(const sa_gunzipper *);
+float sa_gunzipper_kernel_ms(const sa_gunzipper *);    /* the last call's kernels together */
+/* (tests and diagnostics) workgroups a launch uses at most: two per CU, or env SA_GUNZIP_GRID,
+ * read at sa_gunzipper_create like SA_GUNZIP_CHUNK and SA_GUNZIP_RATIO */
+uint32_t sa_gunzipper_grid(const sa_gunzipper *);
+uint32_t sa_gunzipper_chunk(const sa_gunzipper *);     /* bytes per chunk in effect */
+
 #ifdef __cplusplus
 }
 #endif
