@@ -91,7 +91,7 @@ _PATH_NAMES = {"prep": {0: None, 1: "row16", 2: "row64", 3: "fused", 4: "wave"},
                "aux_sort": {0: None, 1: "dense1", 2: "dense2+copy", 3: "raw"},
                "aux_runs": {0: None, 1: "runs_dense", 2: "find_runs"},
                "pass_r": {0: None, 1: "rv0", 2: "rv5", 3: "rv6", 4: "lanes"},
-               "md5": {0: None, 1: "plain", 2: "pipe"}}
+               "md5": {0: None, 1: "plain", 2: "pipe", 3: "wave"}}
 
 
 class _SaPaths(C.Structure):
@@ -500,7 +500,7 @@ class Encoder:
         the fields of sa_paths, the enumerated ones by name (prep: row16 / row64
         / fused / wave; emit: row16 / wave; seq_replay: bucket / full; aux_sort:
         dense1 / dense2+copy / raw; aux_runs: runs_dense / find_runs; pass_r:
-        rv0 / rv5 / rv6 / lanes; md5: plain / pipe; None: the stage did not
+        rv0 / rv5 / rv6 / lanes; md5: plain (a message per lane) / pipe / wave; None: the stage did not
         run), the others as integers (seq_digits / aux_digits: a sort's digit
         widths, four bits a pass, the first pass lowest)."""
         p = _SaPaths()

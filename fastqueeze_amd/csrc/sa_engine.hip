@@ -1380,15 +1380,29 @@ int batch_begin(sa_ctx* c, Batch& B)
         md5t.push_back(Md5Task{I->d_qual.as<uint8_t>() + d.seq_base, d.seq_bytes});
     }
     if (B.pp.md5) {
-        SA_CHECK(c, c->d_md5tasks.ensure(sizeof(Md5Task) * md5t.size()));
+        // the task table, then (k_md5_lanes) the tasks' order: longest first,
+        // 64 consecutive ones to a chain wave (sa_md5_lanes.h)
+        const uint32_t nt = (uint32_t)md5t.size();
+        const size_t task_bytes = sizeof(Md5Task) * md5t.size();
+        std::vector<uint8_t> up(task_bytes + (B.pp.md5 == 1 ? 4 * md5t.size() : 0));
+        memcpy(up.data(), md5t.data(), task_bytes);
+        if (B.pp.md5 == 1) {
+            const std::vector<uint32_t> order = md5l::lane_order(nt, [&](uint32_t i) { return md5t[i].len; });
+            memcpy(up.data() + task_bytes, order.data(), 4 * order.size());
+        }
+        SA_CHECK(c, c->d_md5tasks.ensure(up.size()));
         SA_CHECK(c, c->d_digests.ensure(16 * md5t.size()));
         SA_CHECK(c, hipEventRecord(c->ev_fork, st));
         SA_CHECK(c, hipStreamWaitEvent(c->st2, c->ev_fork, 0));
-        SA_CHECK(c, h2d(c, c->d_md5tasks.p, md5t.data(), sizeof(Md5Task) * md5t.size(), c->st2));
+        SA_CHECK(c, h2d(c, c->d_md5tasks.p, up.data(), up.size(), c->st2));
         ev_begin(c, PH_MD5, c->st2);
-        hipLaunchKernelGGL(B.pp.md5 == 2 ? k_md5<true> : k_md5<false>, dim3((uint32_t)md5t.size()), dim3(128), 0, c->st2,
-                           c->d_md5tasks.as<Md5Task>(),
-                           (uint32_t)md5t.size(), c->d_digests.as<uint32_t>(), c->knobs.md5_prio);
+        if (B.pp.md5 == 1)
+            hipLaunchKernelGGL(k_md5_lanes, dim3(md5l::wave_count(nt)), dim3(128), 0, c->st2, c->d_md5tasks.as<Md5Task>(),
+                               reinterpret_cast<const uint32_t*>(c->d_md5tasks.as<uint8_t>() + task_bytes), nt,
+                               c->d_digests.as<uint32_t>(), c->knobs.md5_prio);
+        else
+            hipLaunchKernelGGL(B.pp.md5 == 2 ? k_md5<true> : k_md5<false>, dim3(nt), dim3(128), 0, c->st2,
+                               c->d_md5tasks.as<Md5Task>(), nt, c->d_digests.as<uint32_t>(), c->knobs.md5_prio);
         ev_finish(c, PH_MD5, c->st2);
         SA_CHECK(c, hipGetLastError());
         SA_CHECK(c, hipEventRecord(c->ev_md5_done, c->st2));

@@ -7,7 +7,8 @@
 //   k_sort_*      per block: stable LSD radix sort of the symbols by model id
 //   k_replay_*    per model: replay the adaptive model in stream order
 //   k_coder       per (block, stream): the serial carry-less range coder
-//   k_md5         per (block, field): RFC1321 digest (runs on a second stream)
+//   k_md5_lanes   per (block, field): RFC1321 digest, a message per lane (runs on a second stream;
+//                 k_md5: the former wave-per-message kernel, SA_MD5_LANES=0)
 //   k_assemble    per block: encaps in doFqzEncode@0x42d2d0 order
 #include <hip/hip_runtime.h>
 
@@ -16,6 +17,7 @@
 #include "sa_common.h"
 #include "sa_device.h"
 #include "sa_logic.h"
+#include "sa_md5_lanes.h"
 
 namespace sa {
 
@@ -3861,6 +3863,149 @@ __global__ __launch_bounds__(128) void k_md5(const Md5Task* __restrict__ tasks, 
     for (uint32_t o = 0; o < tl / 64; o++) md5_block_mk(h, mk[0][o]);
     if (lane == 0)
         for (int k = 0; k < 4; k++) digests[(size_t)t * 4 + k] = h[k];
+}
+
+// ---------------------------------------------------------------------------
+// MD5, one message per lane (sa_md5_lanes.h).  k_md5 spends a whole wave on
+// one message: 64 lanes compute the same digest.  Here the host orders the
+// batch's messages by length and lane l of a chain wave runs the chain of the
+// wave's l-th message, so a batch of 207 messages is 4 chain waves instead of
+// 207.  The step is the same dependent v_bitop3, v_add3, v_alignbit, v_add;
+// the add of K[i] to the message word is a fifth VALU op off the chain.
+//
+// The feed: wave 1 of the workgroup.  Lane l loads its own message's next
+// CHUNK blocks (16-byte loads, a chunk ahead of the LDS writes, so the loads
+// are in flight for a whole chunk of the chain) and writes the raw words to
+// LDS transposed, [block][word][lane]: the chain's reads of a word are 64
+// consecutive dwords.  A message's last one or two blocks (tail, 0x80, the
+// bit count) are built by its lane from guarded reads (md5l::tail_word); a
+// lane past its last block keeps its state by a select.  The chain reads the
+// next block's 16 words while it runs the current block.
+// ---------------------------------------------------------------------------
+#define MD5L_STEP(F, a, b, c, d, i) \
+    a = b + rotl(a + F(b, c, d) + (m[md5l::word_of_step(i)] + md5l::K[i]), (int)md5l::rot_of_step(i))
+
+__device__ __forceinline__ void md5l_block(uint32_t (&h)[4], const uint32_t (&m)[16], bool active)
+{
+    uint32_t a = h[0], b = h[1], c = h[2], d = h[3];
+#define R4(F, i)                    \
+    MD5L_STEP(F, a, b, c, d, i);     \
+    MD5L_STEP(F, d, a, b, c, i + 1); \
+    MD5L_STEP(F, c, d, a, b, i + 2); \
+    MD5L_STEP(F, b, c, d, a, i + 3)
+    R4(MD5_F, 0); R4(MD5_F, 4); R4(MD5_F, 8); R4(MD5_F, 12);
+    R4(MD5_G, 16); R4(MD5_G, 20); R4(MD5_G, 24); R4(MD5_G, 28);
+    R4(MD5_H, 32); R4(MD5_H, 36); R4(MD5_H, 40); R4(MD5_H, 44);
+    R4(MD5_I, 48); R4(MD5_I, 52); R4(MD5_I, 56); R4(MD5_I, 60);
+#undef R4
+    h[0] = active ? h[0] + a : h[0];
+    h[1] = active ? h[1] + b : h[1];
+    h[2] = active ? h[2] + c : h[2];
+    h[3] = active ? h[3] + d : h[3];
+}
+
+__global__ __launch_bounds__(128) void k_md5_lanes(const Md5Task* __restrict__ tasks, const uint32_t* __restrict__ order,
+                                                   uint32_t ntasks, uint32_t* __restrict__ digests, uint32_t prio)
+{
+    constexpr uint32_t CH = md5l::CHUNK, BLK_W = 16 * md5l::LANES;   // (dwords of a block in LDS)
+    __shared__ uint32_t mw[md5l::SLOTS][CH * BLK_W];                 // raw words: [slot][block][word][lane]
+    static_assert(sizeof(mw) == md5l::LDS_BYTES, "md5l::LDS_BYTES");
+    const uint32_t wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    if (wave == 0) set_chain_prio(prio);
+    const uint32_t slot = blockIdx.x * md5l::LANES + lane;
+    const bool have = slot < ntasks;
+    const uint32_t t = have ? order[slot] : 0u;
+    const uint8_t* ptr = have ? tasks[t].ptr : nullptr;
+    const uint64_t len = have ? tasks[t].len : 0;
+    const uint64_t nfull = md5l::full_blocks(len), nblk = have ? md5l::total_blocks(len) : 0;
+    // the wave runs for as many blocks as its longest message
+    uint64_t wb = nblk;
+#pragma unroll
+    for (int o = 32; o; o >>= 1) wb = max(wb, (uint64_t)__shfl_xor((unsigned long long)wb, o));
+    const uint64_t nck = (wb + CH - 1) / CH;
+
+    // ---- the loader's two halves: the chunk's full blocks into registers
+    //      (a lane without a full block reads the task table's first 16 bytes,
+    //      unused), then registers and tail blocks into the LDS slot ----
+    typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+    typedef const __attribute__((address_space(1))) u32x4 g_u4;
+    g_u4* src = nfull ? (g_u4*)ptr : (g_u4*)tasks;
+    const uint64_t last = nfull ? nfull - 1 : 0, str = nfull ? 4 : 0, jstr = nfull ? 1 : 0;
+    u32x4 q[CH][4];
+    auto fetch = [&](uint64_t c) __attribute__((always_inline)) {
+#pragma unroll
+        for (uint32_t k = 0; k < CH; k++) {
+            const uint64_t at = min(c * CH + k, last) * str;
+#pragma unroll
+            for (uint32_t j = 0; j < 4; j++) q[k][j] = src[at + j * jstr];
+        }
+    };
+    auto stash = [&](uint64_t c) __attribute__((always_inline)) {
+        uint32_t* s = mw[c & 1] + lane;
+#pragma unroll
+        for (uint32_t k = 0; k < CH; k++) {
+#pragma unroll
+            for (uint32_t j = 0; j < 4; j++) {
+                uint32_t* w = s + (k * 16 + 4 * j) * md5l::LANES;
+                w[0] = q[k][j].x;
+                w[md5l::LANES] = q[k][j].y;
+                w[2 * md5l::LANES] = q[k][j].z;
+                w[3 * md5l::LANES] = q[k][j].w;
+            }
+        }
+        const uint64_t b0 = c * CH;
+        if (b0 + CH > nfull && b0 < nblk) {   // the chunk holds this lane's tail blocks
+#pragma unroll 1
+            for (uint32_t k = 0; k < CH; k++) {
+                const uint64_t bi = b0 + k;
+                if (bi < nfull || bi >= nblk) continue;
+#pragma unroll 1
+                for (uint32_t w = 0; w < 16; w++) s[(k * 16 + w) * md5l::LANES] = md5l::tail_word(ptr, len, bi, w);
+            }
+        }
+    };
+
+    uint32_t h[4] = {md5l::H0[0], md5l::H0[1], md5l::H0[2], md5l::H0[3]};
+    if (wave == 1) {
+        fetch(0);
+        stash(0);
+        if (nck > 1) fetch(1);
+    }
+    __syncthreads();
+    for (uint64_t c = 0; c < nck; c++) {
+        if (wave == 1) {
+            if (c + 1 < nck) stash(c + 1);
+            if (c + 2 < nck) fetch(c + 2);
+        } else {
+            const uint64_t b0 = c * CH;
+            const uint32_t nb = wb - b0 < CH ? (uint32_t)(wb - b0) : CH;
+            const uint32_t* s = mw[c & 1] + lane;
+            uint32_t ma[16], mb[16];
+#pragma unroll
+            for (uint32_t w = 0; w < 16; w++) ma[w] = s[w * md5l::LANES];
+            for (uint32_t k = 0; k < nb; k += 2) {
+                // (blocks past nb, still inside the slot: read and not used)
+                const uint32_t* s1 = s + min(k + 1, CH - 1) * BLK_W;
+#pragma unroll
+                for (uint32_t w = 0; w < 16; w++) mb[w] = s1[w * md5l::LANES];
+                __builtin_amdgcn_sched_barrier(0);
+                md5l_block(h, ma, b0 + k < nblk);
+                __builtin_amdgcn_sched_barrier(0);
+                if (k + 1 >= nb) break;
+                const uint32_t* s2 = s + min(k + 2, CH - 1) * BLK_W;
+#pragma unroll
+                for (uint32_t w = 0; w < 16; w++) ma[w] = s2[w * md5l::LANES];
+                __builtin_amdgcn_sched_barrier(0);
+                md5l_block(h, mb, b0 + k + 1 < nblk);
+                __builtin_amdgcn_sched_barrier(0);
+            }
+        }
+        __syncthreads();
+    }
+    if (wave == 0 && have) {
+#pragma unroll
+        for (int k = 0; k < 4; k++) digests[(size_t)t * 4 + k] = h[k];
+    }
 }
 
 // ---------------------------------------------------------------------------

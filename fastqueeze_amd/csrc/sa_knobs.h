@@ -85,6 +85,15 @@ struct EngineKnobs {
     // of 60, which costs the co-resident front kernels more than it saves (r2x:
     // 11.6 vs 12.9 GB/s), so SA_MD5_PIPE=1 only
     bool md5_pipe = false;
+    // k_md5_lanes: one message per lane of a chain wave (the bench batch's 207
+    // messages in 4 chain waves) instead of k_md5's wave per message, whose 64
+    // lanes all run the same chain; SA_MD5_LANES=0: k_md5<false> (A/B, fallback).
+    // SA_MD5_PIPE=1 goes before it.  The 207 chain waves at chain priority
+    // took vector issue from the front kernels and L passes on their SIMDs:
+    // the bench 21,289-21,635 against 19,217-19,498 MB/s, three alternating
+    // runs each; front span 129 against 161 ms, L1..L3 39 against 69 ms, MD5
+    // itself 250 against 294 ms a batch (profiles/md5_lanes_ab.json)
+    bool md5_lanes = true;
     // The waits between a context's streams happen on the host thread (which
     // has nothing else to do then) instead of as barrier packets: the boxes run
     // with four hardware queues per process (GPU_MAX_HW_QUEUES=4), so the
@@ -200,6 +209,7 @@ inline EngineKnobs parse_knobs(GetEnv get)
     k.bkt_probe = get("SA_BKT_PROBE");
     k.wg_per_cu = (uint32_t)std::max(1, num("SA_WAVE_GRID", 8));
     k.md5_pipe = nonzero("SA_MD5_PIPE");
+    k.md5_lanes = unless_zero("SA_MD5_LANES");
     k.host_waits = unless_zero("SA_HOST_WAITS");
     const int w = num("SA_CODER_WAVES", 4);
     k.coder_waves = (w == 1 || w == 2) ? (uint32_t)w : 4u;

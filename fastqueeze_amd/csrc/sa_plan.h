@@ -157,7 +157,7 @@ struct PathPlan {
     bool dege_counter;        // k_emit_sq's listed reads from a counter (one a take) for long-read batches
     bool dege_maxq;           // the prep leaves the N / IUPAC maxq (not k_prep_sq: k_emit's serial path)
     int rv_batch;             // pass R's variant (see EngineKnobs::rv_variant)
-    uint32_t md5;             // sa_paths::md5: 0 none, 1 k_md5<false>, 2 k_md5<true>
+    uint32_t md5;             // sa_paths::md5: 0 none, 1 k_md5_lanes, 2 k_md5<true>, 3 k_md5<false>
     bool aux_dense;
     bool skip_long;           // (SA_TEST_SKIP_LONG) no k_replay_aux_long: pass R starves
     // -l R (a batch with qualities): k_rb_spec from a counter on rb_spec_wg
@@ -197,7 +197,7 @@ inline PathPlan plan_paths(const EngineKnobs& k, const RunKnobs& rk, const PathC
     p.rv_batch = k.rv_variant == 0 || k.rv_variant == 5 || k.rv_variant == 6
                      ? k.rv_variant
                      : (sh.nreads && sh.seq_bytes / sh.nreads > 1000 ? 0 : 6);
-    p.md5 = cfg.md5 ? (k.md5_pipe ? 2u : 1u) : 0u;
+    p.md5 = cfg.md5 ? (k.md5_pipe ? 2u : k.md5_lanes ? 1u : 3u) : 0u;
     p.aux_dense = sh.aux_dense;
     p.skip_long = k.test_skip_long;
     p.rblock = cfg.lossy && sh.seq_bytes > 0;

@@ -207,7 +207,7 @@ typedef struct {
     uint32_t host_waits;      /* 1: host-side waits between the context's streams      */
     uint32_t long_grid;       /* k_replay_aux_long workgroups                          */
     uint32_t chain_prio;      /* 1: the chain kernels raise their issue priority       */
-    uint32_t md5;             /* 0: none, 1: k_md5<false>, 2: k_md5<true>              */
+    uint32_t md5;             /* 0: none, 1: k_md5_lanes, 2: k_md5<true>, 3: k_md5<false> */
     uint32_t rblock;          /* 1: the R-Block pre-pass ran                           */
     uint32_t rb_spec_counter; /* 1: k_rb_spec's chunks from a counter, 0: one grid     */
     uint32_t rb_fix_wave;     /* 1: k_rb_fix_w, 0: k_rb_fix                            */
