@@ -441,9 +441,12 @@ SAI_HD uint32_t crc32_share(const uint8_t* data, uint32_t isize, uint32_t lane, 
 }
 
 // ---- BGZF member walk (host) --------------------------------------------------
-// sa_bgzf_scan's body: the walk GzStream::run_bgzf does over a slab.
+// The walk over a slab's members: sa_bgzf_scan's body, and what GzStream's two
+// BGZF paths call (cli_gzstream.h).  max_isize: a member of more text bytes is
+// -2 (INFL_MAX_ISIZE for the device kernel; the host inflate takes any).  ms may
+// be null (the members are counted).
 inline int64_t bgzf_scan(const uint8_t* buf, uint64_t have, sa_bgzf_member* ms, uint64_t max_members, uint64_t* consumed,
-                         uint64_t* out_bytes)
+                         uint64_t* out_bytes, uint32_t max_isize = INFL_MAX_ISIZE)
 {
     uint64_t p = 0, total = 0, n = 0;
     while (p < have) {
@@ -468,7 +471,7 @@ inline int64_t bgzf_scan(const uint8_t* buf, uint64_t have, sa_bgzf_member* ms, 
         const uint8_t* t = h + bsize - 8;
         const uint32_t crc = (uint32_t)(t[0] | t[1] << 8 | t[2] << 16 | (uint32_t)t[3] << 24);
         const uint32_t isize = (uint32_t)(t[4] | t[5] << 8 | t[6] << 16 | (uint32_t)t[7] << 24);
-        if (isize > INFL_MAX_ISIZE) return -2;
+        if (isize > max_isize) return -2;
         if (n >= max_members) return -3;
         if (ms) ms[n] = sa_bgzf_member{p + 12 + xlen, (uint32_t)(bsize - 12 - xlen - 8), total, isize, crc};
         n++;

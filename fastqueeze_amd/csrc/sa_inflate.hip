@@ -101,7 +101,7 @@ int64_t sa_bgzf_scan(const uint8_t* buf, uint64_t have, sa_bgzf_member* ms, uint
                      uint64_t* out_bytes)
 {
     if (!buf && have) return -1;
-    return bgzf_scan(buf, have, ms, max_members, consumed, out_bytes);
+    return bgzf_scan(buf, have, ms, max_members, consumed, out_bytes, INFL_MAX_ISIZE);
 }
 
 sa_inflater* sa_inflater_create(int device)

@@ -72,6 +72,7 @@
 #include <vector>
 
 #include "../../include/seqarc_amd.h"
+#include "cli_gzstream.h"
 #include "cli_knobs.h"
 #include "cli_plan.h"
 
@@ -281,994 +282,12 @@ struct Buf {
     bool empty() const { return n == 0; }
 };
 
-// byte buffers that resize without zero-filling (filled right after)
-template <class T>
-struct NoInitAlloc : std::allocator<T> {
-    template <class U>
-    struct rebind {
-        using other = NoInitAlloc<U>;
-    };
-    NoInitAlloc() = default;
-    template <class U>
-    NoInitAlloc(const NoInitAlloc<U>&) noexcept {}
-    template <class U>
-    void construct(U* p) noexcept
-    {
-        ::new ((void*)p) U;
-    }
-    template <class U, class... A>
-    void construct(U* p, A&&... a)
-    {
-        ::new ((void*)p) U(std::forward<A>(a)...);
-    }
-};
-using Bytes = std::vector<uint8_t, NoInitAlloc<uint8_t>>;
-
 // ---- gzip input -------------------------------------------------------------
-// The reference inflates with gzread on its reader thread.  Here a producer
-// thread per input inflates ahead of the block cut into a bounded queue of
-// chunks.  BGZF files (bgzip: gzip members of <= 64 KiB with the 'BC' extra
-// field giving each member's size) are inflated in parallel: the producer reads
-// a slab of members, `workers` threads inflate them into their places (each
-// member's ISIZE gives its output size) and check their CRCs.  Other gzip files
-// (one member, or several concatenated) inflate on the producer thread.
-// BGZF members are whole raw-deflate streams of known output size: the
-// system's libdeflate (whole-buffer decompression, PCLMUL CRC-32) inflates them
-// at several times zlib 1.2.11's rate.  It is loaded at run time; without it
-// the members go through zlib as before.  (Declared here: the image has the
-// library but no header; these four entry points are libdeflate's stable API.)
-struct LibDeflate {
-    void* (*alloc)() = nullptr;
-    int (*decompress)(void*, const void*, size_t, void*, size_t, size_t*) = nullptr;
-    void (*release)(void*) = nullptr;
-    uint32_t (*crc32)(uint32_t, const void*, size_t) = nullptr;
-    LibDeflate()
-    {
-        if (std::getenv("SA_NO_LIBDEFLATE")) return;   // (A/B)
-        void* h = dlopen("libdeflate.so.0", RTLD_NOW | RTLD_LOCAL);
-        if (!h) return;
-        alloc = reinterpret_cast<void* (*)()>(dlsym(h, "libdeflate_alloc_decompressor"));
-        decompress = reinterpret_cast<int (*)(void*, const void*, size_t, void*, size_t, size_t*)>(
-            dlsym(h, "libdeflate_deflate_decompress"));
-        release = reinterpret_cast<void (*)(void*)>(dlsym(h, "libdeflate_free_decompressor"));
-        crc32 = reinterpret_cast<uint32_t (*)(uint32_t, const void*, size_t)>(dlsym(h, "libdeflate_crc32"));
-        if (!alloc || !decompress || !release || !crc32) alloc = nullptr;
-    }
-    bool ok() const { return alloc != nullptr; }
-};
-const LibDeflate& libdeflate()
-{
-    static const LibDeflate d;
-    return d;
-}
-
-// Inflate threads run at a lower priority than the encoder threads: those
-// sleep on their streams and wake for a few host steps per batch, and with
-// every core inflating they woke late (BGZF short leg, r4i: encode busy 14.3 s
-// against 7.1 s on plain input).
-void lower_priority()
-{
-    (void)setpriority(PRIO_PROCESS, (id_t)syscall(SYS_gettid), 5);
-}
-
-struct GzStream {
-    int fd = -1;
-    int workers = 1;
-    bool bgzf = false;
-    std::thread prod;
-    std::mutex mu;
-    std::condition_variable cv;
-    std::deque<Bytes> q;
-    size_t q_bytes = 0;
-    bool done = false, failed = false, stop = false;
-    Bytes cur;
-    size_t cur_at = 0;
-    static constexpr size_t kMaxQueued = 512u << 20;
-
-    int gpu_device = -1;   // >= 0 (--gpu-inflate): BGZF members are inflated on this device
-    int gunzip_device = -1;   // >= 0 (--gpu-gunzip): gzip that is not BGZF is inflated on this device
-    bool verbose = false;
-    std::string name;
-
-    bool start(int f, int w)
-    {
-        fd = f;
-        workers = std::max(1, w);
-        uint8_t h[18];
-        const ssize_t r = ::pread(fd, h, sizeof h, 0);
-        bgzf = r == 18 && h[0] == 0x1f && h[1] == 0x8b && h[2] == 8 && (h[3] & 4) && h[10] == 6 && h[11] == 0 &&
-               h[12] == 'B' && h[13] == 'C' && h[14] == 2 && h[15] == 0;
-        prod = std::thread([this]() {
-            lower_priority();
-            if (gpu_device >= 0 && !bgzf && gunzip_device < 0 && verbose)
-                fprintf(stderr, "seqarc_amd: --gpu-inflate: %s is gzip but not BGZF, inflating it on the host\n", name.c_str());
-            const bool ok = bgzf ? (gpu_device >= 0 ? run_bgzf_gpu() : run_bgzf()) : gunzip_device >= 0 ? run_plain_gpu() : run_plain();
-            std::lock_guard<std::mutex> g(mu);
-            failed = !ok;
-            done = true;
-            cv.notify_all();
-        });
-        return true;
-    }
-    bool push(Bytes&& v)   // false: the reader went away
-    {
-        std::unique_lock<std::mutex> lk(mu);
-        cv.wait(lk, [&] { return stop || q_bytes < kMaxQueued; });
-        if (stop) return false;
-        q_bytes += v.size();
-        q.push_back(std::move(v));
-        cv.notify_all();
-        return true;
-    }
-    long readn(uint8_t* dst, size_t n, uint64_t& at)
-    {
-        size_t got = 0;
-        while (got < n) {
-            const ssize_t r = ::pread(fd, dst + got, n - got, (off_t)(at + got));
-            if (r < 0 && errno == EINTR) continue;
-            if (r < 0) return -1;
-            if (r == 0) break;
-            got += (size_t)r;
-        }
-        at += got;
-        return (long)got;
-    }
-    // one member or several concatenated (gzread's reading of them)
-    // (at0: the file offset of the first member -- run_host_from continues a file there)
-    bool run_plain(uint64_t at0 = 0)
-    {
-        z_stream z{};
-        if (inflateInit2(&z, 15 + 16) != Z_OK) return false;
-        std::vector<uint8_t> in(4u << 20);
-        uint64_t at = at0;
-        bool eof = false, member_end = false;
-        Bytes out(8u << 20);
-        size_t have = 0;
-        for (;;) {
-            if (z.avail_in == 0 && !eof) {
-                const long r = readn(in.data(), in.size(), at);
-                if (r < 0) { inflateEnd(&z); return false; }
-                if (r == 0) eof = true;
-                z.next_in = in.data();
-                z.avail_in = (uInt)r;
-            }
-            if (z.avail_in == 0 && eof) break;
-            if (member_end) {   // the next member, if it is one (trailing bytes otherwise end the stream)
-                if (z.avail_in < 2 && !eof) {
-                    // (rare: a member boundary at the end of a read slab) keep the byte, read more
-                    memmove(in.data(), z.next_in, z.avail_in);
-                    const long r = readn(in.data() + z.avail_in, in.size() - z.avail_in, at);
-                    if (r < 0) { inflateEnd(&z); return false; }
-                    if (r == 0) eof = true;
-                    z.next_in = in.data();
-                    z.avail_in += (uInt)r;
-                }
-                if (z.avail_in < 2 || z.next_in[0] != 0x1f || z.next_in[1] != 0x8b) break;
-                inflateReset(&z);
-                member_end = false;
-            }
-            z.next_out = out.data() + have;
-            z.avail_out = (uInt)(out.size() - have);
-            const int rc = inflate(&z, Z_NO_FLUSH);
-            have = out.size() - z.avail_out;
-            if (rc == Z_STREAM_END) member_end = true;
-            else if (rc != Z_OK && rc != Z_BUF_ERROR) { inflateEnd(&z); return false; }
-            else if (rc == Z_BUF_ERROR && z.avail_in == 0 && eof) { inflateEnd(&z); return false; }   // truncated
-            if (have == out.size() || (member_end && have > (6u << 20))) {
-                out.resize(have);
-                if (!push(std::move(out))) { inflateEnd(&z); return true; }
-                out = Bytes();
-                out.resize(8u << 20);
-                have = 0;
-            }
-        }
-        inflateEnd(&z);
-        if (!member_end && at > 0) return false;   // ended inside a member
-        out.resize(have);
-        if (have && !push(std::move(out))) return true;
-        return true;
-    }
-    // BGZF: slabs of whole members; a pool of `workers` threads inflates the
-    // members of up to kInFlight slabs (each member into its place, by its
-    // ISIZE; CRC checked), while this thread reads and parses the next slab;
-    // finished slabs leave in order.  (Round 3 started the workers per slab
-    // and joined them before the next one: every slab waited for its slowest
-    // member and the threads' start-up; the outputs were zero-filled first.)
-    bool run_bgzf()
-    {
-        const size_t kSlab = 32u << 20;
-        const size_t kInFlight = 4;
-        struct Mem { size_t off, len; uint64_t out; uint32_t crc, isize; };
-        struct Slab {
-            std::vector<uint8_t> in;
-            std::vector<Mem> ms;
-            Bytes out;
-            size_t next = 0, done = 0;
-            bool bad = false;
-        };
-        std::mutex pm;
-        std::condition_variable pcv;
-        std::deque<std::unique_ptr<Slab>> jobs;   // in file order
-        bool quit = false;
-        auto work = [&]() {
-            lower_priority();
-            const LibDeflate& ld = libdeflate();
-            void* dd = ld.ok() ? ld.alloc() : nullptr;
-            z_stream z{};
-            const bool ok = dd ? true : inflateInit2(&z, -15) == Z_OK;
-            std::unique_lock<std::mutex> lk(pm);
-            for (;;) {
-                Slab* s = nullptr;
-                pcv.wait(lk, [&] {
-                    if (quit) return true;
-                    for (auto& j : jobs)
-                        if (j->next < j->ms.size()) return true;
-                    return false;
-                });
-                if (quit) break;
-                for (auto& j : jobs)
-                    if (j->next < j->ms.size()) { s = j.get(); break; }
-                const size_t i = s->next++;
-                lk.unlock();
-                const Mem& m = s->ms[i];
-                bool bad = !ok;
-                if (ok && m.isize == 0) {   // (the BGZF end-of-file marker: an empty member)
-                    bad = m.crc != 0;
-                } else if (dd) {
-                    size_t got = 0;
-                    const int rc = ld.decompress(dd, s->in.data() + m.off, m.len, s->out.data() + m.out, m.isize, &got);
-                    bad = rc != 0 || got != m.isize || ld.crc32(0, s->out.data() + m.out, m.isize) != m.crc;
-                } else if (ok) {
-                    inflateReset(&z);
-                    z.next_in = s->in.data() + m.off;
-                    z.avail_in = (uInt)m.len;
-                    z.next_out = s->out.data() + m.out;
-                    z.avail_out = (uInt)m.isize;
-                    const int rc = inflate(&z, Z_FINISH);
-                    bad = rc != Z_STREAM_END || z.avail_out != 0 ||
-                          crc32(0L, s->out.data() + m.out, (uInt)m.isize) != m.crc;
-                }
-                lk.lock();
-                s->bad |= bad;
-                if (++s->done == s->ms.size()) pcv.notify_all();
-            }
-            if (dd) ld.release(dd);
-            else if (ok) inflateEnd(&z);
-        };
-        std::vector<std::thread> pool;
-        for (int k = 0; k < workers; k++) pool.emplace_back(work);
-        auto finish = [&](bool rc) {
-            {
-                std::lock_guard<std::mutex> g(pm);
-                quit = true;
-            }
-            pcv.notify_all();
-            for (auto& t : pool) t.join();
-            return rc;
-        };
-        // the oldest slab, once inflated, to the reader (false: failed or the reader went away)
-        auto retire = [&](bool& stopped) -> bool {
-            std::unique_ptr<Slab> s;
-            {
-                std::unique_lock<std::mutex> lk(pm);
-                pcv.wait(lk, [&] { return jobs.front()->done == jobs.front()->ms.size(); });
-                s = std::move(jobs.front());
-                jobs.pop_front();
-            }
-            if (s->bad) return false;
-            if (!s->out.empty() && !push(std::move(s->out))) stopped = true;
-            return true;
-        };
-        std::vector<uint8_t> carry_buf;   // a member cut by the end of the previous slab
-        uint64_t at = 0;
-        bool eof = false, stopped = false;
-        while (!eof || !carry_buf.empty()) {
-            std::unique_ptr<Slab> s(new Slab());
-            s->in.resize(kSlab);
-            const size_t c0 = carry_buf.size();
-            if (c0) memcpy(s->in.data(), carry_buf.data(), c0);
-            carry_buf.clear();
-            const long r = eof ? 0 : readn(s->in.data() + c0, kSlab - c0, at);
-            if (r < 0) return finish(false);
-            if ((size_t)r < kSlab - c0) eof = true;
-            const size_t have = c0 + (size_t)r;
-            size_t p = 0;
-            uint64_t total = 0;
-            while (p + 18 <= have) {
-                const uint8_t* h = s->in.data() + p;
-                if (h[0] != 0x1f || h[1] != 0x8b || h[2] != 8 || !(h[3] & 4)) return finish(false);
-                const size_t xlen = h[10] | (size_t)h[11] << 8;
-                size_t bsize = 0;
-                for (size_t x = 12; x + 4 <= 12 + xlen && p + x + 4 <= have;) {   // the 'BC' subfield
-                    const size_t sl = h[x + 2] | (size_t)h[x + 3] << 8;
-                    if (h[x] == 'B' && h[x + 1] == 'C' && sl == 2) bsize = (h[x + 4] | (size_t)h[x + 5] << 8) + 1;
-                    x += 4 + sl;
-                }
-                if (!bsize || bsize < 12 + xlen + 8) return finish(false);   // not BGZF after all
-                if (p + bsize > have) break;                                // the member continues in the next slab
-                const uint8_t* t = h + bsize - 8;
-                const Mem m{p + 12 + xlen, bsize - 12 - xlen - 8, total,
-                            (uint32_t)(t[0] | t[1] << 8 | t[2] << 16 | (uint32_t)t[3] << 24),
-                            (uint32_t)(t[4] | t[5] << 8 | t[6] << 16 | (uint32_t)t[7] << 24)};
-                total += m.isize;
-                s->ms.push_back(m);
-                p += bsize;
-            }
-            if (s->ms.empty()) {
-                if (eof && have == 0) break;
-                return finish(false);   // a truncated or oversized member, or trailing bytes that are no member
-            }
-            carry_buf.assign(s->in.begin() + (std::ptrdiff_t)p, s->in.begin() + (std::ptrdiff_t)have);
-            if (eof && !carry_buf.empty() && carry_buf.size() < 18) return finish(false);
-            s->out.resize(total);   // (default-initialised: no zero fill)
-            {
-                std::lock_guard<std::mutex> g(pm);
-                jobs.push_back(std::move(s));
-            }
-            pcv.notify_all();
-            size_t n;
-            {
-                std::lock_guard<std::mutex> g(pm);
-                n = jobs.size();
-            }
-            if (n >= kInFlight && !retire(stopped)) return finish(false);
-            if (stopped) return finish(true);
-        }
-        for (;;) {
-            {
-                std::lock_guard<std::mutex> g(pm);
-                if (jobs.empty()) break;
-            }
-            if (!retire(stopped)) return finish(false);
-            if (stopped) return finish(true);
-        }
-        return finish(true);
-    }
-    // BGZF with --gpu-inflate: the same slabs, carry and in-order retirement, but
-    // a slab's members are walked by sa_bgzf_scan and inflated on the device by
-    // sa_inflate_members (one sa_inflater per input, driven by one thread in
-    // place of the `workers` pool) while this thread reads and scans the next
-    // slabs, up to kInFlight ahead.  Slabs are read into recycled page-locked
-    // buffers (the H2D copy is a DMA) and inflate into one of two page-locked
-    // output slabs, from which a copier thread copies the text into the queue's
-    // chunk while the next device call fills the other slab.  Within the gpu
-    // thread H2D, kernel and D2H of a call still run one after the other.
-    bool run_bgzf_gpu()
-    {
-        const size_t kSlab = 32u << 20;
-        const size_t kInFlight = 4;
-        const uint64_t kGroupOut = 512ull << 20;   // output bytes per device call (a slab of long runs inflates 1000-fold)
-        struct Slab {
-            uint8_t* in = nullptr;   // sa_host_alloc, kSlab bytes
-            std::vector<sa_bgzf_member> ms;
-        };
-        auto now = []() { return std::chrono::steady_clock::now(); };
-        auto ms_since = [&](std::chrono::steady_clock::time_point t) {
-            return std::chrono::duration<double, std::milli>(now() - t).count();
-        };
-        const auto t_begin = now();
-        sa_inflater* infl = sa_inflater_create(gpu_device);
-        const double create_ms = ms_since(t_begin);
-        if (!infl) {
-            fprintf(stderr, "seqarc_amd: --gpu-inflate: no usable gfx950 device %d\n", gpu_device);
-            return false;
-        }
-        std::mutex pm;
-        std::condition_variable pcv;
-        std::deque<std::unique_ptr<Slab>> jobs;   // in file order
-        std::vector<uint8_t*> free_in;
-        bool quit = false, bad = false, stopped = false;
-        // -v: where the input's time went (the device calls run one after the other on the gpu
-        // thread, the host copies on the copier thread beside them)
-        double kernel_ms = 0, call_ms = 0, copy_ms = 0, push_ms = 0, alloc_ms = 0, idle_ms = 0, in_alloc_ms = 0, out_wait_ms = 0;
-        uint64_t n_slabs = 0, n_members = 0, text_bytes = 0;
-        std::thread gpu([&]() {
-            lower_priority();
-            // two output slabs: while the copier thread copies one into the queue's chunk,
-            // the next device call fills the other
-            struct Out {
-                uint8_t* p = nullptr;
-                uint64_t cap = 0, bytes = 0;
-                bool busy = false;   // handed to the copier
-            } outs[2];
-            std::mutex cm;
-            std::condition_variable ccv;
-            std::deque<int> handed;   // output slabs to copy, in order
-            bool cquit = false, cgone = false;
-            std::thread copier([&]() {
-                lower_priority();
-                for (;;) {
-                    int k;
-                    {
-                        std::unique_lock<std::mutex> lk(cm);
-                        ccv.wait(lk, [&] { return cquit || !handed.empty(); });
-                        if (handed.empty()) break;
-                        k = handed.front();
-                    }
-                    bool ok = true;
-                    if (!cgone) {   // (only this thread writes cgone)
-                        auto t0 = now();
-                        Bytes chunk(outs[k].bytes);
-                        memcpy(chunk.data(), outs[k].p, outs[k].bytes);
-                        copy_ms += ms_since(t0);
-                        t0 = now();
-                        ok = push(std::move(chunk));
-                        push_ms += ms_since(t0);   // (the queue is full: the block cut is behind)
-                    }
-                    std::lock_guard<std::mutex> g(cm);
-                    if (!ok) cgone = true;
-                    handed.pop_front();
-                    outs[k].busy = false;
-                    ccv.notify_all();
-                }
-            });
-            int turn = 0;
-            std::vector<sa_bgzf_member> grp;
-            for (;;) {
-                std::unique_ptr<Slab> s;
-                {
-                    const auto t0 = now();
-                    std::unique_lock<std::mutex> lk(pm);
-                    pcv.wait(lk, [&] { return quit || !jobs.empty(); });
-                    idle_ms += ms_since(t0);   // (waiting for the reader's next slab)
-                    if (jobs.empty()) break;
-                    s = std::move(jobs.front());   // (it leaves the queue when it is done: the reader counts it in flight)
-                }
-                bool fail = false, gone = false;
-                for (size_t a = 0; a < s->ms.size() && !fail && !gone;) {
-                    size_t b = a;
-                    uint64_t total = 0;
-                    while (b < s->ms.size() && (b == a || total + s->ms[b].isize <= kGroupOut)) total += s->ms[b++].isize;
-                    const uint64_t in0 = s->ms[a].in_off, in1 = s->ms[b - 1].in_off + s->ms[b - 1].in_len;
-                    grp.assign(s->ms.begin() + (std::ptrdiff_t)a, s->ms.begin() + (std::ptrdiff_t)b);
-                    const uint64_t out0 = grp[0].out_off;
-                    for (sa_bgzf_member& m : grp) {
-                        m.in_off -= in0;
-                        m.out_off -= out0;
-                    }
-                    Out& o = outs[turn];
-                    turn ^= 1;
-                    {
-                        const auto t0 = now();
-                        std::unique_lock<std::mutex> lk(cm);
-                        ccv.wait(lk, [&] { return !o.busy; });
-                        out_wait_ms += ms_since(t0);   // (the copier still holds this slab)
-                        if (cgone) {
-                            gone = true;
-                            break;
-                        }
-                    }
-                    if (total > o.cap) {
-                        const auto t0 = now();
-                        if (o.p) sa_host_free(o.p);
-                        o.cap = total + total / 8;
-                        o.p = static_cast<uint8_t*>(sa_host_alloc(o.cap));
-                        if (!o.p) {
-                            fprintf(stderr, "seqarc_amd: --gpu-inflate: cannot allocate %llu bytes of host memory\n",
-                                    (unsigned long long)o.cap);
-                            o.cap = 0;
-                            fail = true;
-                            break;
-                        }
-                        alloc_ms += ms_since(t0);
-                    }
-                    auto t0 = now();
-                    const int rc = sa_inflate_members(infl, s->in + in0, in1 - in0, grp.data(), (uint32_t)grp.size(), o.p, total,
-                                                      nullptr);
-                    if (rc < 0) fprintf(stderr, "seqarc_amd: --gpu-inflate: %s\n", sa_inflater_error(infl));
-                    if (rc != 0) {   // (> 0: members that do not inflate or whose CRC differs -- the host path's error)
-                        fail = true;
-                        break;
-                    }
-                    call_ms += ms_since(t0);
-                    kernel_ms += sa_inflater_kernel_ms(infl);
-                    n_members += grp.size();
-                    text_bytes += total;
-                    if (total) {
-                        std::lock_guard<std::mutex> g(cm);
-                        o.bytes = total;
-                        o.busy = true;
-                        handed.push_back((int)(&o - outs));
-                        ccv.notify_all();
-                    }
-                    a = b;
-                }
-                n_slabs++;
-                std::lock_guard<std::mutex> g(pm);
-                free_in.push_back(s->in);
-                jobs.pop_front();
-                if (fail) bad = true;
-                if (gone) stopped = true;
-                pcv.notify_all();
-                if (fail || gone) break;
-            }
-            {
-                std::lock_guard<std::mutex> g(cm);
-                cquit = true;
-            }
-            ccv.notify_all();
-            copier.join();   // (it copies what was handed to it first)
-            if (cgone) {
-                std::lock_guard<std::mutex> g(pm);
-                stopped = true;
-                pcv.notify_all();
-            }
-            for (Out& o : outs)
-                if (o.p) sa_host_free(o.p);
-        });
-        auto finish = [&](bool rc) {
-            {
-                std::lock_guard<std::mutex> g(pm);
-                quit = true;
-            }
-            pcv.notify_all();
-            gpu.join();   // (it drains the queue unless a slab failed or the reader went away)
-            {
-                std::lock_guard<std::mutex> g(pm);
-                for (auto& j : jobs) free_in.push_back(j->in);
-                jobs.clear();
-                rc = rc && !bad;
-            }
-            for (uint8_t* p : free_in) sa_host_free(p);
-            if (verbose)
-                fprintf(stderr,
-                        "seqarc_amd: --gpu-inflate: %s: %llu slab(s), %llu member(s), %llu text bytes on device %d in %.1f ms: "
-                        "inflater create %.1f ms, slab alloc %.1f + %.1f ms, sa_inflate_members %.1f ms (inflate kernel %.1f ms), "
-                        "host copy %.1f ms beside them (the device thread waited %.1f ms for it), queue wait %.1f ms, waiting for slabs "
-                        "%.1f ms\n",
-                        name.c_str(), (unsigned long long)n_slabs, (unsigned long long)n_members,
-                        (unsigned long long)text_bytes, gpu_device, ms_since(t_begin), create_ms, in_alloc_ms, alloc_ms, call_ms,
-                        kernel_ms, copy_ms, out_wait_ms, push_ms, idle_ms);
-            sa_inflater_destroy(infl);
-            return rc;
-        };
-        std::vector<uint8_t> carry_buf;   // a member cut by the end of the previous slab
-        uint64_t at = 0;
-        bool eof = false;
-        while (!eof || !carry_buf.empty()) {
-            std::unique_ptr<Slab> s(new Slab());
-            {
-                // a slab's buffer: a recycled one, a new one while fewer than kInFlight + 1 exist
-                std::unique_lock<std::mutex> lk(pm);
-                pcv.wait(lk, [&] { return bad || stopped || jobs.size() < kInFlight; });
-                if (bad) { lk.unlock(); return finish(false); }
-                if (stopped) { lk.unlock(); return finish(true); }
-                if (!free_in.empty()) {
-                    s->in = free_in.back();
-                    free_in.pop_back();
-                }
-            }
-            if (!s->in) {
-                const auto t0 = now();
-                s->in = static_cast<uint8_t*>(sa_host_alloc(kSlab));
-                in_alloc_ms += ms_since(t0);
-            }
-            if (!s->in) return finish(false);
-            auto drop = [&](bool rc) {
-                {
-                    std::lock_guard<std::mutex> g(pm);
-                    free_in.push_back(s->in);
-                }
-                return finish(rc);
-            };
-            const size_t c0 = carry_buf.size();
-            if (c0) memcpy(s->in, carry_buf.data(), c0);
-            carry_buf.clear();
-            const long r = eof ? 0 : readn(s->in + c0, kSlab - c0, at);
-            if (r < 0) return drop(false);
-            if ((size_t)r < kSlab - c0) eof = true;
-            const size_t have = c0 + (size_t)r;
-            if (eof && have == 0) return drop(true);
-            s->ms.resize(have / 26 + 1);   // (a member is at least 26 bytes: header 18, no deflate bytes, trailer 8)
-            uint64_t consumed = 0, total = 0;
-            const int64_t n = sa_bgzf_scan(s->in, have, s->ms.data(), s->ms.size(), &consumed, &total);
-            // not BGZF after all; or no whole member: a truncated member, or trailing bytes that are no member
-            if (n <= 0) return drop(false);
-            s->ms.resize((size_t)n);
-            carry_buf.assign(s->in + consumed, s->in + have);
-            if (eof && !carry_buf.empty() && carry_buf.size() < 18) return drop(false);
-            {
-                std::lock_guard<std::mutex> g(pm);
-                jobs.push_back(std::move(s));
-            }
-            pcv.notify_all();
-        }
-        {
-            std::unique_lock<std::mutex> lk(pm);
-            pcv.wait(lk, [&] { return bad || stopped || jobs.empty(); });
-        }
-        return finish(true);
-    }
-    // The rest of a gzip file on the host, from where sa_gunzip_run left it: inside
-    // a deflate stream a raw inflate with the state's window as its dictionary,
-    // primed with the bits left of the current byte, the member's running CRC-32
-    // and length carried on and compared with the trailer here; the members after
-    // it through run_plain.
-    bool run_host_from(const sa_gunzip_state& gs, uint64_t at)
-    {
-        if (gs.ended) return true;
-        if (gs.in_stream) {
-            z_stream z{};
-            if (inflateInit2(&z, -15) != Z_OK) return false;
-            auto fail = [&]() {
-                inflateEnd(&z);
-                return false;
-            };
-            if (gs.win_len && inflateSetDictionary(&z, gs.window + (32768 - gs.win_len), gs.win_len) != Z_OK) return fail();
-            std::vector<uint8_t> in(4u << 20);
-            Bytes out(8u << 20);
-            size_t have = 0;
-            uint32_t crc = gs.crc;
-            uint64_t len = gs.len;
-            bool eof = false, first = true, end = false;
-            while (!end) {
-                if (z.avail_in == 0) {
-                    const long r = eof ? 0 : readn(in.data(), in.size(), at);
-                    if (r <= 0) return fail();   // a read error, or the file ends inside the member
-                    z.next_in = in.data();
-                    z.avail_in = (uInt)r;
-                    if (first && gs.bit) {
-                        if (inflatePrime(&z, 8 - (int)gs.bit, in[0] >> gs.bit) != Z_OK) return fail();
-                        z.next_in++;
-                        z.avail_in--;
-                    }
-                    first = false;
-                }
-                z.next_out = out.data() + have;
-                z.avail_out = (uInt)(out.size() - have);
-                const int rc = inflate(&z, Z_NO_FLUSH);
-                const size_t now_have = out.size() - z.avail_out;
-                crc = (uint32_t)crc32(crc, out.data() + have, (uInt)(now_have - have));
-                len += now_have - have;
-                have = now_have;
-                if (rc == Z_STREAM_END) end = true;
-                else if (rc != Z_OK && rc != Z_BUF_ERROR) return fail();
-                if (have == out.size() || end) {
-                    out.resize(have);
-                    if (have && !push(std::move(out))) {
-                        inflateEnd(&z);
-                        return true;
-                    }
-                    out = Bytes();
-                    out.resize(8u << 20);
-                    have = 0;
-                }
-            }
-            // the trailer: what inflate left of the slab, then the file
-            uint8_t t[8];
-            size_t k = std::min<size_t>(8, z.avail_in);
-            memcpy(t, z.next_in, k);
-            at -= z.avail_in - k;   // (readn moved `at` past the slab)
-            inflateEnd(&z);
-            if (k < 8 && readn(t + k, 8 - k, at) != (long)(8 - k)) return false;
-            const uint32_t tcrc = t[0] | t[1] << 8 | t[2] << 16 | (uint32_t)t[3] << 24;
-            const uint32_t tlen = t[4] | t[5] << 8 | t[6] << 16 | (uint32_t)t[7] << 24;
-            if (tcrc != crc || tlen != (uint32_t)len) return false;
-        }
-        // the next member, if it is one (trailing bytes otherwise end the stream)
-        uint8_t m[2];
-        uint64_t peek = at;
-        if (readn(m, 2, peek) != 2 || m[0] != 0x1f || m[1] != 0x8b) return true;
-        return run_plain(at);
-    }
-    // Gzip that is not BGZF with --gpu-gunzip: run_bgzf_gpu's shape around
-    // sa_gunzip_run.  This thread reads the file into recycled page-locked slabs,
-    // up to kInFlight ahead, each with room in front; the device thread puts what
-    // the last call left unconsumed (the unconfirmed tail of its slab) into that
-    // room and inflates carry + slab into one of two page-locked output slabs,
-    // from which the copier thread copies the text into the queue's chunk while
-    // the next call fills the other.  A call of two chunks or more that confirms
-    // less than one chunk of compressed bytes (stored-only files, runs of enormous
-    // ratio, many tiny members: one wave does all the work), or leaves more than
-    // the room holds, ends the device path: the host continues from the state
-    // (run_host_from).
-    bool run_plain_gpu()
-    {
-        const size_t kSlab = 32u << 20;
-        const size_t kRoom = 8u << 20;   // in front of a slab: the carry
-        const size_t kInFlight = 4;
-        const uint64_t kOutCap = 512ull << 20;
-        struct Slab {
-            uint8_t* in = nullptr;   // sa_host_alloc, kRoom + kSlab bytes
-            size_t have = 0;
-            uint64_t file_at = 0;
-            bool last = false;
-        };
-        auto now = []() { return std::chrono::steady_clock::now(); };
-        auto ms_since = [&](std::chrono::steady_clock::time_point t) {
-            return std::chrono::duration<double, std::milli>(now() - t).count();
-        };
-        const auto t_begin = now();
-        sa_gunzipper* gz = sa_gunzipper_create(gunzip_device);
-        const double create_ms = ms_since(t_begin);
-        if (!gz) {
-            fprintf(stderr, "seqarc_amd: --gpu-gunzip: no usable gfx950 device %d\n", gunzip_device);
-            return false;
-        }
-        const uint64_t chunk = sa_gunzipper_chunk(gz);
-        std::mutex pm;
-        std::condition_variable pcv;
-        std::deque<std::unique_ptr<Slab>> jobs;   // in file order
-        std::vector<uint8_t*> free_in;
-        bool quit = false, bad = false, stopped = false, takeover = false;
-        std::unique_ptr<sa_gunzip_state> gs(new sa_gunzip_state());
-        uint64_t host_at = 0;   // takeover: the file offset the host continues at
-        double kernel_ms[5] = {}, call_ms = 0, copy_ms = 0, push_ms = 0, alloc_ms = 0, idle_ms = 0, in_alloc_ms = 0, out_wait_ms = 0;
-        uint64_t n_calls = 0, n_chunks = 0, n_cand = 0, n_conf = 0, n_false = 0, n_members = 0, text_bytes = 0;
-        std::thread gpu([&]() {
-            lower_priority();
-            struct Out {
-                uint8_t* p = nullptr;
-                uint64_t cap = 0, bytes = 0;
-                bool busy = false;   // handed to the copier
-            } outs[2];
-            std::mutex cm;
-            std::condition_variable ccv;
-            std::deque<int> handed;   // output slabs to copy, in order
-            bool cquit = false, cgone = false;
-            std::thread copier([&]() {
-                lower_priority();
-                for (;;) {
-                    int k;
-                    {
-                        std::unique_lock<std::mutex> lk(cm);
-                        ccv.wait(lk, [&] { return cquit || !handed.empty(); });
-                        if (handed.empty()) break;
-                        k = handed.front();
-                    }
-                    bool ok = true;
-                    if (!cgone) {   // (only this thread writes cgone)
-                        auto t0 = now();
-                        Bytes chunk_out(outs[k].bytes);
-                        memcpy(chunk_out.data(), outs[k].p, outs[k].bytes);
-                        copy_ms += ms_since(t0);
-                        t0 = now();
-                        ok = push(std::move(chunk_out));
-                        push_ms += ms_since(t0);   // (the queue is full: the block cut is behind)
-                    }
-                    std::lock_guard<std::mutex> g(cm);
-                    if (!ok) cgone = true;
-                    handed.pop_front();
-                    outs[k].busy = false;
-                    ccv.notify_all();
-                }
-            });
-            int turn = 0;
-            std::vector<uint8_t> carry;   // what the last call left of its input
-            bool fail = false, gone = false, leave = false, over = false;
-            while (!fail && !gone && !leave && !over) {
-                std::unique_ptr<Slab> s;
-                {
-                    const auto t0 = now();
-                    std::unique_lock<std::mutex> lk(pm);
-                    pcv.wait(lk, [&] { return quit || !jobs.empty(); });
-                    idle_ms += ms_since(t0);   // (waiting for the reader's next slab)
-                    if (jobs.empty()) break;
-                    s = std::move(jobs.front());   // (it leaves the queue when it is done: the reader counts it in flight)
-                }
-                // carry + slab, contiguous; then again with what is left, until a call needs the next slab
-                uint8_t* in = s->in + kRoom - carry.size();
-                size_t n = carry.size() + s->have;
-                uint64_t in_at = s->file_at - carry.size();   // the file offset of in[0]
-                if (!carry.empty()) memcpy(in, carry.data(), carry.size());
-                carry.clear();
-                for (;;) {
-                    Out& o = outs[turn];
-                    turn ^= 1;
-                    {
-                        const auto t0 = now();
-                        std::unique_lock<std::mutex> lk(cm);
-                        ccv.wait(lk, [&] { return !o.busy; });
-                        out_wait_ms += ms_since(t0);   // (the copier still holds this slab)
-                        if (cgone) {
-                            gone = true;
-                            break;
-                        }
-                    }
-                    const uint64_t want = std::min<uint64_t>(kOutCap, 6ull * n + (64u << 20));
-                    if (want > o.cap) {
-                        const auto t0 = now();
-                        if (o.p) sa_host_free(o.p);
-                        o.cap = want;
-                        o.p = static_cast<uint8_t*>(sa_host_alloc(o.cap));
-                        if (!o.p) {
-                            fprintf(stderr, "seqarc_amd: --gpu-gunzip: cannot allocate %llu bytes of host memory\n",
-                                    (unsigned long long)o.cap);
-                            o.cap = 0;
-                            fail = true;
-                            break;
-                        }
-                        alloc_ms += ms_since(t0);
-                    }
-                    const auto t0 = now();
-                    uint64_t out_bytes = 0, in_used = 0;
-                    sa_gunzip_info info{};
-                    const int rc = sa_gunzip_run(gz, in, n, s->last ? 1 : 0, gs.get(), o.p, o.cap, &out_bytes, &in_used, &info);
-                    if (rc < 0) fprintf(stderr, "seqarc_amd: --gpu-gunzip: %s\n", sa_gunzipper_error(gz));
-                    if (rc > 0)
-                        fprintf(stderr, "seqarc_amd: --gpu-gunzip: %s: the gzip stream is corrupt (status %d near byte %llu)\n",
-                                name.c_str(), rc, (unsigned long long)(in_at + in_used));
-                    if (rc != 0) {   // (> 0: the host path's error)
-                        fail = true;
-                        break;
-                    }
-                    call_ms += ms_since(t0);
-                    const float k[5] = {info.find_ms, info.spec_ms, info.chain_ms, info.resolve_ms, info.crc_ms};
-                    for (int i = 0; i < 5; i++) kernel_ms[i] += k[i];
-                    n_calls++;
-                    n_chunks += info.chunks;
-                    n_cand += info.candidates;
-                    n_conf += info.waves_confirmed;
-                    n_false += info.false_skipped;
-                    n_members += info.members_ended;
-                    text_bytes += out_bytes;
-                    if (out_bytes) {
-                        std::lock_guard<std::mutex> g(cm);
-                        o.bytes = out_bytes;
-                        o.busy = true;
-                        handed.push_back((int)(&o - outs));
-                        ccv.notify_all();
-                    }
-                    in += in_used;
-                    n -= in_used;
-                    in_at += in_used;
-                    if (gs->ended || (s->last && n == 0)) {
-                        over = true;
-                        break;
-                    }
-                    // (one wave confirmed in a call of four chunks or more: the stream has no block starts
-                    // to find -- stored or fixed blocks only -- and one wave would go on doing all the work)
-                    const bool low = (info.chunks >= 2 && in_used < chunk) || (s->last && !in_used && !out_bytes) ||
-                                     (info.chunks >= 4 && info.waves_confirmed == 1 && info.end_why != SA_GZ_OUTCAP);
-                    if (low || (!s->last && n > kRoom)) {
-                        leave = true;
-                        host_at = in_at;
-                        if (verbose)
-                            fprintf(stderr,
-                                    "seqarc_amd: --gpu-gunzip: %s: a call of %u chunk(s) confirmed %llu compressed bytes (wave %u "
-                                    "ended it: %u); the host takes over at byte %llu\n",
-                                    name.c_str(), info.chunks, (unsigned long long)in_used, info.end_wave, info.end_why,
-                                    (unsigned long long)host_at);
-                        break;
-                    }
-                    // the next slab goes behind what is left, unless this is the last: then what is left runs alone
-                    if (!s->last && (info.end_why != SA_GZ_OUTCAP && info.end_why != SA_GZ_BREAKS && info.end_why != SA_GZ_FULL)) break;
-                    if (!s->last && n < chunk) break;
-                }
-                if (!fail && !gone && !leave && !over) carry.assign(in, in + n);
-                std::lock_guard<std::mutex> g(pm);
-                free_in.push_back(s->in);
-                jobs.pop_front();
-                if (fail) bad = true;
-                if (gone || over) stopped = true;
-                if (leave) takeover = true;
-                pcv.notify_all();
-            }
-            {
-                std::lock_guard<std::mutex> g(cm);
-                cquit = true;
-            }
-            ccv.notify_all();
-            copier.join();   // (it copies what was handed to it first)
-            if (cgone) {
-                std::lock_guard<std::mutex> g(pm);
-                stopped = true;
-                takeover = false;
-                pcv.notify_all();
-            }
-            for (Out& o : outs)
-                if (o.p) sa_host_free(o.p);
-        });
-        auto finish = [&](bool rc) {
-            {
-                std::lock_guard<std::mutex> g(pm);
-                quit = true;
-            }
-            pcv.notify_all();
-            gpu.join();   // (it drains the queue unless a call failed, the path left or the reader went away)
-            {
-                std::lock_guard<std::mutex> g(pm);
-                for (auto& j : jobs) free_in.push_back(j->in);
-                jobs.clear();
-                rc = rc && !bad;
-            }
-            for (uint8_t* p : free_in) sa_host_free(p);
-            if (verbose)
-                fprintf(stderr,
-                        "seqarc_amd: --gpu-gunzip: %s: %llu call(s), %llu chunk(s), %llu candidate(s), %llu wave(s) confirmed, %llu false "
-                        "candidate(s) skipped, %llu member(s), %llu text bytes on device %d in %.1f ms: gunzipper create %.1f ms, slab "
-                        "alloc %.1f + %.1f ms, sa_gunzip_run %.1f ms (gunzip kernels: find %.1f, spec %.1f, chain %.1f, resolve %.1f, "
-                        "crc %.1f ms), host copy %.1f ms beside them (the device thread waited %.1f ms for it), queue wait %.1f ms, "
-                        "waiting for slabs %.1f ms%s\n",
-                        name.c_str(), (unsigned long long)n_calls, (unsigned long long)n_chunks, (unsigned long long)n_cand,
-                        (unsigned long long)n_conf, (unsigned long long)n_false, (unsigned long long)n_members,
-                        (unsigned long long)text_bytes, gunzip_device, ms_since(t_begin), create_ms, in_alloc_ms, alloc_ms, call_ms,
-                        kernel_ms[0], kernel_ms[1], kernel_ms[2], kernel_ms[3], kernel_ms[4], copy_ms, out_wait_ms, push_ms, idle_ms,
-                        takeover ? "; the host inflated the rest" : "");
-            sa_gunzipper_destroy(gz);
-            if (rc && takeover) rc = run_host_from(*gs, host_at);
-            return rc;
-        };
-        uint64_t at = 0;
-        bool eof = false;
-        while (!eof) {
-            std::unique_ptr<Slab> s(new Slab());
-            {
-                // a slab's buffer: a recycled one, a new one while fewer than kInFlight + 1 exist
-                std::unique_lock<std::mutex> lk(pm);
-                pcv.wait(lk, [&] { return bad || stopped || takeover || jobs.size() < kInFlight; });
-                if (bad) { lk.unlock(); return finish(false); }
-                if (stopped || takeover) { lk.unlock(); return finish(true); }
-                if (!free_in.empty()) {
-                    s->in = free_in.back();
-                    free_in.pop_back();
-                }
-            }
-            if (!s->in) {
-                const auto t0 = now();
-                s->in = static_cast<uint8_t*>(sa_host_alloc(kRoom + kSlab));
-                in_alloc_ms += ms_since(t0);
-            }
-            if (!s->in) return finish(false);
-            s->file_at = at;
-            const long r = readn(s->in + kRoom, kSlab, at);
-            if (r < 0) {
-                {
-                    std::lock_guard<std::mutex> g(pm);
-                    free_in.push_back(s->in);
-                }
-                return finish(false);
-            }
-            if ((size_t)r < kSlab) eof = true;
-            s->have = (size_t)r;
-            s->last = eof;
-            {
-                std::lock_guard<std::mutex> g(pm);
-                jobs.push_back(std::move(s));
-            }
-            pcv.notify_all();
-        }
-        {
-            std::unique_lock<std::mutex> lk(pm);
-            pcv.wait(lk, [&] { return bad || stopped || takeover || jobs.empty(); });
-        }
-        return finish(true);
-    }
-    // up to n bytes into dst; 0 at the end; -1 on a gzip error
-    long read(uint8_t* dst, size_t n)
-    {
-        size_t got = 0;
-        while (got < n) {
-            if (cur_at == cur.size()) {
-                std::unique_lock<std::mutex> lk(mu);
-                cv.wait(lk, [&] { return !q.empty() || done; });
-                if (q.empty()) {
-                    if (failed) return -1;
-                    break;
-                }
-                cur = std::move(q.front());
-                q.pop_front();
-                q_bytes -= cur.size();
-                cur_at = 0;
-                cv.notify_all();
-            }
-            const size_t k = std::min(n - got, cur.size() - cur_at);
-            memcpy(dst + got, cur.data() + cur_at, k);
-            cur_at += k;
-            got += k;
-        }
-        return (long)got;
-    }
-    ~GzStream()
-    {
-        {
-            std::lock_guard<std::mutex> g(mu);
-            stop = true;
-            cv.notify_all();
-        }
-        if (prod.joinable()) prod.join();
-    }
-};
+// GzStream (cli_gzstream.h) inflates a gzip input ahead of the block cut on
+// threads of its own; its two device paths call the library through this table.
+const GzDevice kGzDevice = {sa_host_alloc,      sa_host_free,          sa_inflater_create, sa_inflater_destroy,
+                            sa_inflater_error,  sa_inflater_kernel_ms, sa_inflate_members, sa_gunzipper_create,
+                            sa_gunzipper_destroy, sa_gunzipper_chunk,  sa_gunzipper_error, sa_gunzip_run};
 
 // ---- input ---------------------------------------------------------------
 // getFileType@0x40d9f0 (gzip magic); plain files are read with read(2) /
@@ -1291,7 +310,7 @@ struct Input {
         unsigned char m[2] = {0, 0};
         is_gz = ::pread(fd, m, 2, 0) == 2 && m[0] == 0x1f && m[1] == 0x8b;
         if (is_gz) {
-            gz.reset(new GzStream());
+            gz.reset(new GzStream(kGzDevice));
             gz->gpu_device = g_gpu_inflate_dev;
             gz->gunzip_device = g_gpu_gunzip_dev;
             gz->verbose = g_gz_verbose;

@@ -8,9 +8,10 @@
 //     the 64 lane shares>"; with outdir, member i's output goes to outdir/i.
 //     Each member's input and output live in heap blocks of exactly their
 //     sizes, so a sanitizer build sees any access outside them.
-//   inflate_emu scan <file> <max_members>
+//   inflate_emu scan <file> <max_members> [max_isize]
 //     sa_bgzf_scan's walk over the file: "<ret> <consumed> <out_bytes>", then
-//     per member "<in_off> <in_len> <out_off> <isize> <crc>".
+//     per member "<in_off> <in_len> <out_off> <isize> <crc>".  max_isize: the
+//     walk's limit on a member's ISIZE (default: sa_bgzf_scan's, 65536).
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -52,7 +53,8 @@ int main(int argc, char** argv)
         const uint64_t maxm = strtoull(argv[3], nullptr, 10);
         std::vector<sa_bgzf_member> ms(maxm);
         uint64_t consumed = 0, out_bytes = 0;
-        const int64_t n = bgzf_scan(f.data(), f.size(), ms.data(), maxm, &consumed, &out_bytes);
+        const uint32_t max_isize = argc >= 5 ? (uint32_t)strtoul(argv[4], nullptr, 10) : INFL_MAX_ISIZE;
+        const int64_t n = bgzf_scan(f.data(), f.size(), ms.data(), maxm, &consumed, &out_bytes, max_isize);
         printf("%lld %llu %llu\n", (long long)n, (unsigned long long)consumed, (unsigned long long)out_bytes);
         for (int64_t i = 0; i < n; i++)
             printf("%llu %u %llu %u %u\n", (unsigned long long)ms[i].in_off, ms[i].in_len,
@@ -60,7 +62,7 @@ int main(int argc, char** argv)
         return 0;
     }
     if (argc < 3 || strcmp(argv[1], "members")) {
-        fprintf(stderr, "usage: inflate_emu members <file> [outdir] | scan <file> <max_members>\n");
+        fprintf(stderr, "usage: inflate_emu members <file> [outdir] | scan <file> <max_members> [max_isize]\n");
         return 2;
     }
     const std::vector<uint8_t> f = slurp(argv[2]);

@@ -324,10 +324,11 @@ def test_malformed_under_sanitizers(emu, tmp_path):
 
 
 # ---- sa_bgzf_scan ------------------------------------------------------------
-def _scan_emu(exe, tmp_path, data, maxm):
+def _scan_emu(exe, tmp_path, data, maxm, max_isize=None):
     f = tmp_path / "scan.bin"
     f.write_bytes(data)
-    r = subprocess.run([str(exe), "scan", str(f), str(maxm)], capture_output=True, check=True)
+    r = subprocess.run([str(exe), "scan", str(f), str(maxm)] + ([str(max_isize)] if max_isize is not None else []),
+                       capture_output=True, check=True)
     lines = r.stdout.decode().split("\n")[:-1]
     ret, consumed, out_bytes = map(int, lines[0].split())
     return ret, consumed, out_bytes, [tuple(map(int, ln.split())) for ln in lines[1:]]
@@ -384,3 +385,21 @@ def test_bgzf_scan(emu, tmp_path):
                 assert got[0] == expect, (name, how, got[:3])
             else:
                 assert got == expect, (name, how, got[:3])
+
+
+def test_bgzf_scan_isize_limit(emu, tmp_path):
+    """A member of more than 65,536 text bytes (the format's BSIZE bounds only its
+    compressed size): -2 with the device kernel's limit, which sa_bgzf_scan
+    passes, and walked like any other with no limit, as the host inflate wants it."""
+    big = b"A" * 100_000
+    cd = deflate(big)
+    z = bgzf(b"ACGT" * 1000)[:-len(EOF_MEMBER)] + bgzf_member(cd, len(big), zlib.crc32(big)) + EOF_MEMBER
+    first = len(z) - len(EOF_MEMBER) - (18 + len(cd) + 8)
+    want = [(18, first - 26, 0, 4000, zlib.crc32(b"ACGT" * 1000)), (first + 18, len(cd), 4000, len(big), zlib.crc32(big)),
+            (len(z) - 10, 2, 4000 + len(big), 0, 0)]
+    assert _scan_emu(emu[0], tmp_path, z, 16, 0xffffffff) == (3, len(z), 4000 + len(big), want)
+    assert _scan_emu(emu[0], tmp_path, z, 16, 100_000) == (3, len(z), 4000 + len(big), want)
+    for limit in (None, 65536, 99_999):
+        assert _scan_emu(emu[0], tmp_path, z, 16, limit)[0] == -2, limit
+    lib = _scan_lib(z, 16)
+    assert lib is None or lib[0] == -2
