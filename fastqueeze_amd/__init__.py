@@ -158,6 +158,18 @@ def load_library(path: str | None = None):
         "sa_gunzip_run": ([P, P, U64, I32, P, P, U64, P, P, P], I32),
         "sa_gunzipper_error": ([P], C.c_char_p), "sa_gunzipper_kernel_ms": ([P], C.c_float),
         "sa_gunzipper_grid": ([P], C.c_uint32), "sa_gunzipper_chunk": ([P], C.c_uint32),
+        "sa_cut_next_se": ([P, U64, I32, U64, P, U64], I64),
+        "sa_cut_next_pe": ([P, U64, I32, P, U64, I32, U64, P, U64, P, P], I32),
+        "sa_devtext_create": ([I32, U64], P), "sa_devtext_destroy": ([P], None),
+        "sa_devtext_error": ([P], C.c_char_p), "sa_devtext_avail": ([P], U64), "sa_devtext_room": ([P], U64),
+        "sa_devtext_append": ([P, P, U64], I32), "sa_inflate_members_dev": ([P, P, U64, P, C.c_uint32, P, P], I32),
+        "sa_devtext_peek": ([P, U64, P, U64], I32),
+        "sa_devtext_cut": ([P, I32, P, I32, U64, P, U64, P, P, U64, P], I64),
+        "sa_devtext_take": ([P, U64, P, U64], P), "sa_devblock_release": ([P], None),
+        "sa_devblock_lens": ([P, P, P], I32), "sa_devblock_fetch": ([P, P, P], I32),
+        "sa_devblock_pool_trim": ([I32], None),
+        "sa_text_upload_dev": ([P, P, I32, I32, I32, P, U64], I32), "sa_upload_error": ([P], C.c_char_p),
+        "sa_devtext_kernel_ms": ([P, P, P], None), "sa_devtext_count_bytes": ([P], U64),
     }
     for name, (args, res) in sigs.items():
         fn = getattr(lib, name)
@@ -235,6 +247,26 @@ def cut_pe(t1, t2, block_size: int = BLOCK_SIZE):
     x = [0] + e1[:n].astype(np.int64).tolist()
     y = [0] + e2[:n].astype(np.int64).tolist()
     return [((x[i], x[i + 1]), (y[i], y[i + 1])) for i in range(n)]
+
+
+def cut_next_se(win, eof: bool, block_size: int, first) -> int | None:
+    """sa_cut_next_se: the next block's bytes in a window, or None (read more / no cut)."""
+    lib = load_library()
+    w, f = _as_u8(win), _as_u8(first)
+    dummy = np.zeros(1, np.uint8)
+    r = lib.sa_cut_next_se(_ptr(w) or dummy.ctypes.data, w.size, 1 if eof else 0, block_size, _ptr(f), f.size)
+    return None if r < 0 else int(r)
+
+
+def cut_next_pe(w1, eof1: bool, w2, eof2: bool, block_size: int, first) -> tuple[int, int] | None:
+    """sa_cut_next_pe: the next block's bytes of each input, or None (read more / no cut)."""
+    lib = load_library()
+    a, b, f = _as_u8(w1), _as_u8(w2), _as_u8(first)
+    dummy = np.zeros(1, np.uint8)
+    e1, e2 = C.c_uint64(0), C.c_uint64(0)
+    r = lib.sa_cut_next_pe(_ptr(a) or dummy.ctypes.data, a.size, 1 if eof1 else 0, _ptr(b) or dummy.ctypes.data, b.size,
+                           1 if eof2 else 0, block_size, _ptr(f), f.size, C.byref(e1), C.byref(e2))
+    return None if r != 0 else (int(e1.value), int(e2.value))
 
 
 def _alloc(nbytes: int):
@@ -372,6 +404,28 @@ class Encoder:
         self._staged = [int(info[i].out_bound) for i in range(len(keep))]
         return [{"nreads": int(info[i].nreads), "len_long": int(info[i].len_long),
                  "name_bytes": int(info[i].name_bytes), "seq_bytes": int(info[i].seq_bytes)} for i in range(len(keep))]
+
+    def stage_devblocks(self, blocks: "list[DevBlock]", slot: int = 0) -> list[dict]:
+        """sa_text_upload_dev of each devblock (device to device) into text arena
+        `slot`, then sa_text_parse: the blocks staged as stage_text stages their
+        texts, which never were on the host.  Returns per-block counts as stage_text does."""
+        lens = [b.lens for b in blocks]
+        stride = max([max(l1, l2) for l1, l2 in lens] + [1])
+        for i, b in enumerate(blocks):
+            if self._lib.sa_text_upload_dev(self._ctx, None, slot, i, len(blocks), b._h, stride) != 0:
+                self._staged = None
+                raise SeqArcError(f"sa_text_upload_dev: {self._lib.sa_upload_error(self._ctx).decode()}")
+        dummy = np.zeros(1, np.uint8)   # (text1 / text2 only tell SE from PE)
+        arr = (_SaTextBlock * max(1, len(blocks)))(*[
+            _SaTextBlock(dummy.ctypes.data, l1, dummy.ctypes.data if b.paired else None, l2)
+            for b, (l1, l2) in zip(blocks, lens)])
+        info = (_SaTextInfo * max(1, len(blocks)))()
+        if self._lib.sa_text_parse(self._ctx, None, slot, arr, len(blocks), stride, info) != 0:
+            self._staged = None
+            self._err("sa_text_parse")
+        self._staged = [int(info[i].out_bound) for i in range(len(blocks))]
+        return [{"nreads": int(info[i].nreads), "len_long": int(info[i].len_long),
+                 "name_bytes": int(info[i].name_bytes), "seq_bytes": int(info[i].seq_bytes)} for i in range(len(blocks))]
 
     def run(self, cfg: Config):
         c = cfg._c()
@@ -613,6 +667,18 @@ class Inflater:
             raise SeqArcError(f"sa_inflate_members ({rc}): {self._lib.sa_inflater_error(self._h).decode()}")
         return rc, status[:ms.size]
 
+    def inflate_to(self, devtext: "DevText", data, members: np.ndarray) -> tuple[int, np.ndarray]:
+        """sa_inflate_members_dev: the members' text appended to the devtext, never
+        on the host; (return value, status).  -3: more text than devtext.room (nothing done)."""
+        a = _as_u8(data)
+        ms = np.ascontiguousarray(members, BGZF_MEMBER)
+        status = np.zeros(max(1, ms.size), np.uint32)
+        rc = self._lib.sa_inflate_members_dev(self._h, _ptr(a), a.size, ms.ctypes.data, ms.size, devtext._h,
+                                              status.ctypes.data)
+        if rc < 0 and rc != -3:
+            raise SeqArcError(f"sa_inflate_members_dev ({rc}): {self._lib.sa_inflater_error(self._h).decode()}")
+        return rc, status[:ms.size]
+
     def inflate_members(self, data, members: np.ndarray) -> tuple[bytes, np.ndarray]:
         """The members' output (a buffer that ends with the last member's bytes;
         a failed member's range is undefined) and the per-member status."""
@@ -635,6 +701,115 @@ class Inflater:
             raise SeqArcError(f"BGZF member {i} failed to inflate: status {int(status[i])} "
                               f"({INFLATE_STATUS.get(int(status[i]), '?')})")
         return out
+
+
+CUT_MORE, CUT_DONE, CUT_FULL, CUT_NONE = 1, 2, 3, 4   # SA_CUT_*: why DevText.cut stopped
+
+
+class DevBlock:
+    """One block's text in device memory (sa_devblock), as DevText.take cut it."""
+
+    def __init__(self, handle):
+        self._lib = load_library()
+        self._h = handle
+        l1, l2 = C.c_uint64(0), C.c_uint64(0)
+        self.paired = bool(self._lib.sa_devblock_lens(handle, C.byref(l1), C.byref(l2)))
+        self.lens = (int(l1.value), int(l2.value))
+
+    def fetch(self) -> tuple[bytes, bytes | None]:
+        """The block's texts copied to the host."""
+        a = np.empty(self.lens[0], np.uint8)
+        b = np.empty(self.lens[1], np.uint8)
+        dummy = np.zeros(1, np.uint8)
+        if self._lib.sa_devblock_fetch(self._h, _ptr(a) or dummy.ctypes.data, _ptr(b) or dummy.ctypes.data) != 0:
+            raise SeqArcError("sa_devblock_fetch failed")
+        return a.tobytes(), (b.tobytes() if self.paired else None)
+
+    def close(self):
+        if self._h:
+            self._lib.sa_devblock_release(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class DevText:
+    """One input's FASTQ text as a stream in device memory (sa_devtext): appended
+    from the host or inflated into by Inflater.inflate_to, cut on the device."""
+
+    def __init__(self, capacity: int, device: int = 0):
+        self._lib = load_library()
+        self._h = self._lib.sa_devtext_create(device, capacity)
+        if not self._h:
+            raise SeqArcError(f"sa_devtext_create failed: no usable gfx950 device {device}, or no memory")
+
+    def close(self):
+        if self._h:
+            self._lib.sa_devtext_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _err(self, what: str):
+        raise SeqArcError(f"{what}: {self._lib.sa_devtext_error(self._h).decode()}")
+
+    @property
+    def avail(self) -> int:
+        return int(self._lib.sa_devtext_avail(self._h))
+
+    @property
+    def room(self) -> int:
+        return int(self._lib.sa_devtext_room(self._h))
+
+    @property
+    def kernel_ms(self) -> tuple[float, float]:
+        """Device time of the last newline count and the last cut."""
+        a, b = C.c_float(0), C.c_float(0)
+        self._lib.sa_devtext_kernel_ms(self._h, C.byref(a), C.byref(b))
+        return float(a.value), float(b.value)
+
+    @property
+    def count_bytes(self) -> int:
+        return int(self._lib.sa_devtext_count_bytes(self._h))
+
+    def append(self, data):
+        a = _as_u8(data)
+        if self._lib.sa_devtext_append(self._h, _ptr(a), a.size) != 0:
+            self._err("sa_devtext_append")
+
+    def peek(self, off: int, n: int) -> bytes:
+        out = np.empty(n, np.uint8)
+        if self._lib.sa_devtext_peek(self._h, off, _ptr(out), n) != 0:
+            self._err("sa_devtext_peek")
+        return out.tobytes()
+
+    def cut(self, block_size: int, first, eof: bool = True, mate: "DevText | None" = None, mate_eof: bool | None = None,
+            max_blocks: int = 4096) -> tuple[list[tuple[int, int]], int]:
+        """sa_devtext_cut: ([(len1, len2)] of the blocks the unread text holds, CUT_*)."""
+        f = _as_u8(first)
+        l1 = np.zeros(max_blocks, np.uint64)
+        l2 = np.zeros(max_blocks, np.uint64)
+        end = C.c_int32(0)
+        e2 = eof if mate_eof is None else mate_eof
+        n = self._lib.sa_devtext_cut(self._h, 1 if eof else 0, mate._h if mate is not None else None, 1 if e2 else 0,
+                                     block_size, _ptr(f), f.size, _ptr(l1), _ptr(l2), max_blocks, C.byref(end))
+        if n < 0:
+            self._err("sa_devtext_cut")
+        return list(zip(l1[:n].astype(np.int64).tolist(), l2[:n].astype(np.int64).tolist())), int(end.value)
+
+    def take(self, len1: int, mate: "DevText | None" = None, len2: int = 0) -> DevBlock:
+        h = self._lib.sa_devtext_take(self._h, len1, mate._h if mate is not None else None, len2)
+        if not h:
+            self._err("sa_devtext_take")
+        return DevBlock(h)
 
 
 class GunzipState(C.Structure):

@@ -27,6 +27,10 @@ struct PlanOpts {
     // ahead instead: 21.5-25.4)
     int read_threads = 16;
     bool host_only = false, host_parse = false, ingest_only = false, ramp = false, stage_ahead = false;
+    // --gpu-text applies (the command line sets it in the plan's input once it knows the inputs
+    // are BGZF): the text stays on the device, so the feed is the streamed one and the reader
+    // holds no page-locked windows
+    bool gpu_text = false;
 };
 
 struct PlanIn : PlanOpts {
@@ -121,7 +125,7 @@ inline BatchPlan plan_batches(const PlanIn& in, const CliKnobs& kn, int64_t nctx
     p.texts_pinned = p.dev_parse && !in.ingest_only;
     p.seg_plain = in.read_threads > 0 && !gz && !kn.windows && known;
     p.early_read = kn.early_read && p.seg_plain;
-    if (p.texts_pinned && !p.seg_plain) {
+    if (p.texts_pinned && !p.seg_plain && !in.gpu_text) {
         p.prefill_windows = (size_t)nin * (2 * (size_t)std::max(1, in.batch) + 4);
         if (known && !gz) p.prefill_windows = std::min(p.prefill_windows, (size_t)nin * (size_t)(mx / p.cut_window + 3));
         if (kn.prefill_windows_set) p.prefill_windows = (size_t)kn.prefill_windows;
@@ -137,7 +141,7 @@ inline BatchPlan plan_batches(const PlanIn& in, const CliKnobs& kn, int64_t nctx
             p.B = (est + p.C - 1) / p.C;
         }
     }
-    p.stream_opt = p.dev_parse && !in.ingest_only && !in.stage_ahead && kn.stream;
+    p.stream_opt = p.dev_parse && !in.ingest_only && !in.stage_ahead && (kn.stream || in.gpu_text);
     p.max_inflight = (size_t)p.B * ((size_t)p.C * (p.stream_opt ? 2 : 1) + 2);
     for (int64_t k = 0; p.ramp && k < p.C; k++)
         p.ramp_start.push_back(p.ramp_start.back() + std::max<int64_t>(1, p.B * (k + 1) / (p.C + 1)));

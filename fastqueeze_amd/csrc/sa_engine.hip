@@ -199,6 +199,7 @@ struct sa_ctx {
     // device while this context's kernels run
     hipStream_t st_copy = nullptr;
     std::mutex copy_mu;
+    std::string upload_err;   // sa_text_upload_dev's error text, under copy_mu (never c->err: sa_run may be running)
     // the dense AUX sort's flag (EngineKnobs::aux_dense to begin with).  The
     // emit's target buffer depends on the number of passes, so the batch follows
     // this context's previous one: a batch with more than 512 models in a block
@@ -2154,6 +2155,7 @@ int sa_encode_blocks(sa_ctx* ctx, const sa_block* in, int n, const sa_cfg* cfg, 
 // FASTQ text parsed on the device (sa_stage_text)
 #include "sa_parse.hip"
 #include "sa_inflate.hip"
+#include "sa_devtext.hip"
 #include "sa_gunzip.hip"
 
 // the HASH reference-index path

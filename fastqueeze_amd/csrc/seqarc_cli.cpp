@@ -26,6 +26,9 @@
 //   --ingest-only    the reader and block cut alone, batches dealt to devices x contexts
 //                    consumers (no device); --ingest-crc: the consumers CRC the texts
 //   --gpu-inflate    BGZF inputs are inflated on the first device (sa_inflate_members)
+//   --gpu-text       BGZF inputs are inflated into device memory and stay there: the block
+//                    cut runs on the device and the blocks reach the parse device to device
+//                    (sa_devtext; one device, device parse; off by default)
 //                    instead of on host threads; other gzip files keep the host path
 //   --gpu-gunzip     gzip inputs that are not BGZF (gzip, pigz, concatenated members) are
 //                    inflated on the first device by speculation (sa_gunzip_run)
@@ -84,13 +87,15 @@ int usage()
             "usage: seqarc_amd -c [-t N] [-l R] [-n] [-f] [-p] -1 A.fq[.gz] [-2 B.fq[.gz]] (-o OUT | OUT)\n"
             "                  [--slevel K] [--qlevel Q] [--devices N] [--contexts K] [--batch BLOCKS]\n"
             "                  [--block-size MiB] [--device D] [--share-device] [--ramp] [--release]\n"
-            "                  [--stage-ahead] [--writers N] [--read-threads N] [--gpu-inflate]\n"
+            "                  [--stage-ahead] [--writers N] [--read-threads N] [--gpu-inflate] [--gpu-text]\n"
             "                  [--gpu-gunzip]\n"
             "       seqarc_amd -d [-t N] [-f] [-p] [-P 1|2|3] [ref.fa] ARCHIVE.arc [PREFIX] [-o PREFIX]\n"
             "       seqarc_amd -i ref.fa            (HASH index: ref.fa.hash + ref.fa.md5)\n"
             "       (-s with -i / -c / -d and ref.fa: the index image in /dev/shm/<ref file name>)\n"
             "       (-c / -d with ref.fa: the reference path; -I N insert size, --maxmis M)\n"
             "       (--gpu-inflate: BGZF inputs of -c are inflated on the first device, not on host threads)\n"
+            "       (--gpu-text: BGZF inputs of -c are inflated, cut into blocks and parsed on the device, the text\n"
+            "        never on the host; not with --ingest-only, --host-only, --host-parse, --stage-ahead)\n"
             "       (--gpu-gunzip: gzip inputs of -c that are not BGZF are inflated on the first device)\n");
     return 2;
 }
@@ -303,13 +308,14 @@ struct Input {
     std::unique_ptr<GzStream> gz;
     bool is_gz = false, eof = false, seekable = true;
     uint64_t off = 0;   // file offset of the next byte (plain files)
-    bool open(const char* path)
+    // raw: a gzip input is not inflated here (--gpu-text: a DevInput reads the file)
+    bool open(const char* path, bool raw = false)
     {
         fd = ::open(path, O_RDONLY);
         if (fd < 0) return false;
         unsigned char m[2] = {0, 0};
         is_gz = ::pread(fd, m, 2, 0) == 2 && m[0] == 0x1f && m[1] == 0x8b;
-        if (is_gz) {
+        if (is_gz && !raw) {
             gz.reset(new GzStream(kGzDevice));
             gz->gpu_device = g_gpu_inflate_dev;
             gz->gunzip_device = g_gpu_gunzip_dev;
@@ -390,6 +396,154 @@ struct Input {
     {
         gz.reset();
         if (fd >= 0) ::close(fd);
+    }
+};
+
+// the file starts with a BGZF member header (GzStream::start's test)
+bool is_bgzf_file(const char* path)
+{
+    const int fd = ::open(path, O_RDONLY);
+    if (fd < 0) return false;
+    uint8_t h[18];
+    const ssize_t r = ::pread(fd, h, sizeof h, 0);
+    ::close(fd);
+    return r == 18 && h[0] == 0x1f && h[1] == 0x8b && h[2] == 8 && (h[3] & 4) && h[10] == 6 && h[11] == 0 && h[12] == 'B' &&
+           h[13] == 'C' && h[14] == 2 && h[15] == 0;
+}
+
+// --gpu-text: one BGZF input inflated into a devtext (sa_devtext), where the
+// block cut finds it.  The compressed side is --gpu-inflate's: a file thread
+// reads slabs of whole members (GzStream::BgzfReader: the carry, the member
+// walk, its three errors) and publishes them through a SlabFeed.  There is no
+// output side: the reader thread of the pipeline (read_device) takes the
+// oldest slab and calls sa_inflate_members_dev with as many of its members as
+// the devtext has room for -- one thread drives the devtext.
+struct DevInput {
+    struct Slab {
+        uint8_t* in = nullptr;   // sa_host_alloc, slab_bytes
+        std::vector<sa_bgzf_member> ms;
+    };
+    static constexpr uint64_t kCapacity = 1ull << 30;   // the devtext's bytes (per mate)
+    static constexpr uint64_t kCall = 256ull << 20;     // text bytes of one device call at most
+    GzStream gz{kGzDevice};   // never started: the BgzfReader's view of the file (fd, slab_bytes, readn)
+    SlabFeed<Slab> feed{kGzDevice, 4};
+    sa_inflater* infl = nullptr;
+    sa_devtext* dt = nullptr;
+    std::string name;
+    bool file_bad = false;   // (under feed.pm) the file thread ended on an error
+    // ---- the reader thread's ----
+    Slab* cur = nullptr;     // the slab being inflated and its next member
+    size_t at = 0;
+    bool eof = false, started = false, closed = false;
+    std::vector<sa_bgzf_member> grp;
+    uint64_t members = 0, text_bytes = 0, calls = 0;   // (-v)
+    double kernel_ms = 0, count_ms = 0, call_ms = 0;
+
+    bool start(int fd, const char* path, int device, std::string& err)
+    {
+        name = path;
+        gz.fd = fd;
+        gz.name = path;
+        infl = sa_inflater_create(device);
+        dt = infl ? sa_devtext_create(device, kCapacity) : nullptr;
+        if (!infl || !dt) {
+            err = "--gpu-text: no usable gfx950 device " + std::to_string(device) + ", or no device memory for the text";
+            return false;
+        }
+        feed.device = std::thread([this]() {   // (SlabFeed joins it in finish(); here it is the file's reader)
+            lower_priority();
+            GzStream::BgzfReader rd{gz};
+            bool ok = true;
+            while (rd.more()) {
+                std::unique_ptr<Slab> s(new Slab());
+                s->in = feed.get(gz.slab_bytes);
+                if (!s->in) break;   // (the pipeline's reader stopped, or no memory: feed.bad)
+                uint64_t total = 0;
+                // (a member of more than 65,536 text bytes is an error: the kernel's window holds no more)
+                const int got = rd.next(s->in, s->ms, total, sa::INFL_MAX_ISIZE);
+                if (got <= 0) {
+                    feed.put_back(s->in);
+                    ok = got == 0;
+                    break;
+                }
+                feed.publish(std::move(s));
+            }
+            {   // the end: the slabs still queued are taken, then next() gives nullptr
+                std::lock_guard<std::mutex> g(feed.pm);
+                file_bad = !ok || feed.bad;
+                feed.quit = true;
+            }
+            feed.pcv.notify_all();
+        });
+        started = true;
+        return true;
+    }
+    // inflates into the devtext until it holds `want` bytes or the input is used up; false: err
+    bool pump(uint64_t want, std::string& err)
+    {
+        while (!eof && sa_devtext_avail(dt) < want) {
+            if (!cur) {
+                cur = feed.next();
+                at = 0;
+                if (!cur) {
+                    std::lock_guard<std::mutex> g(feed.pm);
+                    if (file_bad) {
+                        err = "read error on " + name + " (not BGZF throughout, a member cut short, or bytes after the last member)";
+                        return false;
+                    }
+                    eof = true;
+                    break;
+                }
+            }
+            // members [at, b): what the devtext has room for, at most kCall text bytes
+            const uint64_t room = std::min<uint64_t>(sa_devtext_room(dt), kCall);
+            size_t b = at;
+            uint64_t total = 0;
+            while (b < cur->ms.size() && total + cur->ms[b].isize <= room) total += cur->ms[b++].isize;
+            if (b == at) {   // (want is far below the capacity: a devtext short of it has room for a member)
+                err = "--gpu-text: the device text of " + name + " has no room for a member";
+                return false;
+            }
+            const uint64_t in0 = cur->ms[at].in_off, in1 = cur->ms[b - 1].in_off + cur->ms[b - 1].in_len;
+            grp.assign(cur->ms.begin() + (std::ptrdiff_t)at, cur->ms.begin() + (std::ptrdiff_t)b);
+            for (sa_bgzf_member& m : grp) m.in_off -= in0;
+            const auto t0 = gz_now();
+            const int rc = sa_inflate_members_dev(infl, cur->in + in0, in1 - in0, grp.data(), (uint32_t)grp.size(), dt, nullptr);
+            if (rc != 0) {   // (> 0: members that do not inflate or whose CRC differs -- the host path's error)
+                err = rc < 0 ? std::string("--gpu-text: ") + sa_inflater_error(infl) : "read error on " + name + " (a BGZF member does not inflate, or its CRC differs)";
+                return false;
+            }
+            call_ms += gz_ms_since(t0);
+            kernel_ms += sa_inflater_kernel_ms(infl);
+            float cms = 0;
+            sa_devtext_kernel_ms(dt, &cms, nullptr);
+            count_ms += cms;
+            members += grp.size();
+            text_bytes += total;
+            calls++;
+            at = b;
+            if (at == cur->ms.size()) {
+                feed.retire(false, false, false);
+                cur = nullptr;
+            }
+        }
+        return true;
+    }
+    // the reader thread, on every way out: the file thread ended and joined, the slabs freed
+    void close()
+    {
+        if (!started || closed) return;
+        closed = true;
+        if (cur) feed.retire(false, true, false);
+        else feed.reader_gone();
+        cur = nullptr;
+        feed.finish();
+    }
+    ~DevInput()
+    {
+        close();
+        if (infl) sa_inflater_destroy(infl);
+        if (dt) sa_devtext_destroy(dt);
     }
 };
 
@@ -820,6 +974,11 @@ struct Job {                     // one block between the reader and the writer
     Buf<uint8_t> out;             // the encoded block
     int state = 0;                // 0 read, 1 parsed, 2 encoded
     uint32_t crc = 0;             // --ingest-only: CRC-32 of t1 then t2 (the writer folds them in order)
+    sa_devblock* dblk = nullptr;  // --gpu-text: the block's text on the device (t1 / t2: block 0 only, for the ID template)
+    Job() = default;
+    Job(const Job&) = delete;
+    Job& operator=(const Job&) = delete;
+    ~Job() { if (dblk) sa_devblock_release(dblk); }
 };
 
 // The archive file, written by several threads (round 5).  A block's place
@@ -1036,7 +1195,8 @@ bool parse_job(Job& j, bool pe, ParsedPool& pool, TextPool& texts, bool keep_tex
 struct Options : cli::PlanOpts {   // (PlanOpts, cli_plan.h: the options the batch plan reads)
     const char *f1 = nullptr, *f2 = nullptr, *out = nullptr, *arc = nullptr, *ref = nullptr;
     bool compress = false, decompress = false, index = false, force = false, in_dir = false, share_device = false,
-         verbose = false, release = false, shm = false, maxmis_set = false, ingest_crc = false, gpu_inflate = false, gpu_gunzip = false;
+         verbose = false, release = false, shm = false, maxmis_set = false, ingest_crc = false, gpu_inflate = false, gpu_gunzip = false,
+         gpu_text = false;   // --gpu-text: BGZF inputs inflated, cut and parsed on the device (DevInput, read_device)
     int writers = 8;        // --writers: the archive writer's copy threads (ArcWriter; 1: write(2) in order)
     int pipe = 0, device = 0, block_mib = 50, maxmis = 7;
     int insert = 0;
@@ -1412,6 +1572,9 @@ struct Pipeline {
     const bool pe;
     Stamps st;
     Input in1, in2;
+    // --gpu-text applies: the inputs are BGZF and their text lives in these (read_device)
+    bool dev_text = false;
+    std::unique_ptr<DevInput> dv1, dv2;
     std::string path;
     cli::PlanIn pin;
     cli::BatchPlan plan;
@@ -1480,7 +1643,15 @@ struct Pipeline {
                 return false;
             }
         }
-        if (!in1.open(o.f1) || (pe && !in2.open(o.f2))) {
+        // --gpu-text takes BGZF inputs on one device; anything else runs as it would without the switch
+        if (o.gpu_text) {
+            const bool bgzf = is_bgzf_file(o.f1) && (!pe || is_bgzf_file(o.f2));
+            dev_text = bgzf && o.devices == 1;
+            if (!dev_text && o.verbose)
+                fprintf(stderr, "seqarc_amd: --gpu-text does not apply (%s): running without it\n",
+                        !bgzf ? "an input is not BGZF" : "more than one device");
+        }
+        if (!in1.open(o.f1, dev_text) || (pe && !in2.open(o.f2, dev_text))) {
             fprintf(stderr, "seqarc_amd: cannot open the input\n");
             return false;
         }
@@ -1489,6 +1660,7 @@ struct Pipeline {
         path = outp + ".arc";
         if (!may_write(path, o.force)) return false;
         static_cast<cli::PlanOpts&>(pin) = o;
+        pin.gpu_text = dev_text;
         pin.pe = pe;
         pin.bs = (uint64_t)o.block_mib << 20;   // BlockSize(M), default 50 (param+0x1b78)
         pin.hw_threads = std::thread::hardware_concurrency();
@@ -1607,7 +1779,8 @@ struct Pipeline {
                 st.seg_freed = st.now();
             });
         reader = std::thread([this]() {
-            if (segr) read_segments();
+            if (dev_text) read_device();
+            else if (segr) read_segments();
             else read_windows();
         });
     }
@@ -1770,6 +1943,94 @@ struct Pipeline {
         }
     }
 
+    // --gpu-text: BGZF inputs whose text stays on the device.  Each mate's
+    // devtext is pumped to a cut window (DevInput::pump: sa_inflate_members_dev),
+    // sa_devtext_cut cuts every block the text holds, and each block leaves as a
+    // devblock in its Job -- the encoders upload it device to device (upload).
+    // Block 0 is also fetched to the host: the parser needs it for the ID template.
+    void read_device()
+    {
+        constexpr uint64_t kCut = 64;   // blocks per cut call at most
+        const uint64_t want = plan.cut_window;
+        std::vector<uint8_t> first;
+        std::vector<uint64_t> l1(kCut), l2(kCut);
+        double room_wait = 0, cut_ms = 0;
+        uint64_t cuts = 0;
+        std::string e;
+        auto done = [&]() {   // every way out: the file threads joined; -v: where the inputs' time went
+            for (DevInput* d : {dv1.get(), dv2.get()}) {
+                if (!d) continue;
+                d->close();
+                if (o.verbose)
+                    fprintf(stderr,
+                            "seqarc_amd: --gpu-text: %s: %llu member(s), %llu text bytes in %llu call(s) on device %d: "
+                            "sa_inflate_members_dev %.3f s (inflate kernel %.3f s, newline count %.1f ms); cut %.1f ms over "
+                            "%lld blocks in %llu call(s); waited %.3f s for room\n",
+                            d->name.c_str(), (unsigned long long)d->members, (unsigned long long)d->text_bytes,
+                            (unsigned long long)d->calls, o.device, d->call_ms / 1e3, d->kernel_ms / 1e3, d->count_ms, cut_ms,
+                            (long long)nread_local, (unsigned long long)cuts, room_wait);
+            }
+        };
+        dv1.reset(new DevInput());
+        if (pe) dv2.reset(new DevInput());
+        if (!dv1->start(in1.fd, o.f1, o.device, e) || (pe && !dv2->start(in2.fd, o.f2, o.device, e))) return done(), fail(e);
+        for (int64_t i = 0;;) {
+            const double tf0 = st.now();
+            const uint64_t had = sa_devtext_avail(dv1->dt) + (pe ? sa_devtext_avail(dv2->dt) : 0);
+            if (!dv1->pump(want, e) || (pe && !dv2->pump(want, e))) return done(), fail(e);
+            const uint64_t a1 = sa_devtext_avail(dv1->dt), a2 = pe ? sa_devtext_avail(dv2->dt) : 0;
+            if (i == 0) {   // the first line and the bare-'+' test, on peeked bytes
+                if (a1 == 0 && a2 == 0) return done(), end_input(0);
+                std::vector<uint8_t> h1, h2;
+                auto peek = [&](DevInput& d, uint64_t a, std::vector<uint8_t>& h) {   // the first three lines at least
+                    for (uint64_t n = std::min<uint64_t>(a, 1u << 20);; n = std::min(a, want)) {
+                        h.resize((size_t)n);
+                        if (sa_devtext_peek(d.dt, 0, h.data(), n) != 0) return false;
+                        if (n >= std::min(a, want) || std::count(h.begin(), h.end(), (uint8_t)'\n') >= 3) return true;
+                    }
+                };
+                if (!peek(*dv1, a1, h1) || (pe && !peek(*dv2, a2, h2)))
+                    return done(), fail(std::string("--gpu-text: ") + sa_devtext_error(dv1->dt));
+                capture_first(first, h1.data(), h1.size(), h2.data(), h2.size());
+            }
+            const double tc0 = st.now();
+            st.fill_busy += tc0 - tf0;
+            int32_t end = 0;
+            const int64_t n = sa_devtext_cut(dv1->dt, dv1->eof, pe ? dv2->dt : nullptr, pe && dv2->eof, pin.bs, first.data(),
+                                             first.size(), l1.data(), l2.data(), kCut, &end);
+            if (n < 0) return done(), fail(std::string("--gpu-text: ") + sa_devtext_error(dv1->dt));
+            float cms = 0;
+            sa_devtext_kernel_ms(dv1->dt, nullptr, &cms);
+            cut_ms += cms;
+            cuts++;
+            st.cut_busy += st.now() - tc0;
+            for (int64_t b = 0; b < n; b++, i++) {
+                const double tw = st.now();
+                if (!wait_for_room()) return done();
+                room_wait += st.now() - tw;
+                std::unique_ptr<Job> j(new Job());
+                j->dblk = sa_devtext_take(dv1->dt, l1[(size_t)b], pe ? dv2->dt : nullptr, pe ? l2[(size_t)b] : 0);
+                if (!j->dblk) return done(), fail(std::string("--gpu-text: ") + sa_devtext_error(dv1->dt));
+                if (i == 0) {
+                    j->t1.resize((size_t)l1[0]);
+                    if (pe) j->t2.resize((size_t)l2[0]);
+                    if (sa_devblock_fetch(j->dblk, j->t1.data(), pe ? j->t2.data() : nullptr) != 0)
+                        return done(), fail("--gpu-text: cannot fetch block 0");
+                }
+                const bool last = b == n - 1 && end == SA_CUT_DONE;
+                nread_local = i + 1;
+                if (last) done();
+                publish(i, std::move(j), l1[(size_t)b], pe ? l2[(size_t)b] : 0, last);
+                if (last) return;
+            }
+            if (end == SA_CUT_DONE) return done(), end_input(i);
+            if (end == SA_CUT_NONE) return done(), fail(pe ? "PE block cut failed (mates out of step)" : "block cut failed");
+            if (end == SA_CUT_MORE && n == 0 && sa_devtext_avail(dv1->dt) + (pe ? sa_devtext_avail(dv2->dt) : 0) == had)
+                return done(), fail("--gpu-text: the block cut asks for more text than the device text holds");
+        }
+    }
+    int64_t nread_local = 0;   // (read_device's own count of its blocks, for its -v line)
+
     // ---- stage: the parsers (host parse; with the device parse block 0 only,
     // for the ID template) ----
     void start_parsers() { for (int t = 0; t < plan.nparse; t++) parsers.emplace_back([this]() { parse_loop(); }); }
@@ -1929,7 +2190,14 @@ struct Pipeline {
             }
             const sa_text_block tb = text_of(*j);
             const double t0 = st.now();
-            if (sa_text_upload(ctx, nullptr, slot, (int)(i - b0), (int)(b1 - b0), &tb, plan.tstride) != 0)
+            if (j->dblk) {   // --gpu-text: the text is on the device already
+                if (sa_text_upload_dev(ctx, nullptr, slot, (int)(i - b0), (int)(b1 - b0), j->dblk, plan.tstride) != 0)
+                    return fail(std::string("staging failed: ") + sa_upload_error(ctx)), false;
+                sa_devblock_release(j->dblk);
+                j->dblk = nullptr;
+                j->t1.release();   // (block 0's host copy: the parser is done with it)
+                j->t2.release();
+            } else if (sa_text_upload(ctx, nullptr, slot, (int)(i - b0), (int)(b1 - b0), &tb, plan.tstride) != 0)
                 return fail(std::string("staging failed: ") + sa_last_error(ctx)), false;
             give_back(*j, texts);   // (the device holds the text now)
             {
@@ -2595,6 +2863,7 @@ int main(int argc, char** argv)
         else if (!strcmp(a, "--ingest-crc")) o.ingest_crc = true;
         else if (!strcmp(a, "--gpu-inflate")) o.gpu_inflate = true;
         else if (!strcmp(a, "--gpu-gunzip")) o.gpu_gunzip = true;
+        else if (!strcmp(a, "--gpu-text")) o.gpu_text = true;
         else if (!strcmp(a, "--read-threads")) { if (!ival(o.read_threads, 0)) return usage(); }
         else if (!strcmp(a, "--writers")) { if (!ival(o.writers, 1)) return usage(); }
         else if (!strcmp(a, "--no-ramp")) o.ramp = false;
@@ -2646,6 +2915,11 @@ int main(int argc, char** argv)
         o.out = p;
     }
     if (!o.f1 || !o.out) return usage();
+    if (o.gpu_text && (o.ingest_only || o.host_only || o.host_parse || o.stage_ahead)) {
+        fprintf(stderr, "seqarc_amd: --gpu-text keeps the text on the device: not with --ingest-only, --host-only, "
+                        "--host-parse or --stage-ahead\n");
+        return usage();
+    }
     // one hardware queue per stream (four per context): with the runtime's
     // default of four queues (which the GPU boxes preset), the contexts' streams
     // share queues and one context's packets wait behind another's (DESIGN.md

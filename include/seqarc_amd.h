@@ -520,6 +520,81 @@ float sa_gunzipper_kernel_ms(const sa_gunzipper *);    /* the last call's kernel
 uint32_t sa_gunzipper_grid(const sa_gunzipper *);
 uint32_t sa_gunzipper_chunk(const sa_gunzipper *);     /* bytes per chunk in effect */
 
+/* ---- text resident on the device: sa_devtext --------------------------------
+ * One input's FASTQ text as a stream in device memory: a linear buffer with a read and a
+ * write position and a stream of its own; no sa_ctx needed.  Text arrives by sa_devtext_append
+ * (from the host) or sa_inflate_members_dev (BGZF members inflated straight into it), the block
+ * cut of sa_cut_next_se / sa_cut_next_pe runs on the device (sa_devtext_cut, k_dt_cut), a block
+ * leaves as a sa_devblock, made by sa_devtext_take, and reaches an encoder's text arena by
+ * sa_text_upload_dev; sa_text_parse then works as after sa_text_upload.  The text never
+ * crosses to the host: per block only its lengths do.
+ * Threads: one thread at a time drives a devtext (append, inflate, cut, take, peek).  A
+ * devblock is a copy and belongs to whoever holds it: another thread may upload or fetch it
+ * while the devtext goes on.  Every call returns with its device work done. */
+typedef struct sa_devtext sa_devtext;
+typedef struct sa_devblock sa_devblock;
+/* why sa_devtext_cut stopped */
+enum {
+    SA_CUT_MORE = 1,   /* the next block needs more text (the host cut's "read more")        */
+    SA_CUT_DONE = 2,   /* every input is at eof and empty                                   */
+    SA_CUT_FULL = 3,   /* max_blocks blocks were cut                                        */
+    SA_CUT_NONE = 4    /* a full window without a cut (the host cut's -1: mates out of step) */
+};
+sa_devtext *sa_devtext_create(int device, uint64_t capacity);   /* NULL: no gfx950 device, or no memory */
+void sa_devtext_destroy(sa_devtext *);
+const char *sa_devtext_error(const sa_devtext *);
+uint64_t sa_devtext_avail(const sa_devtext *);   /* bytes between the read and the write position */
+/* bytes an append can take now: capacity - avail.  When the room behind the write position
+ * is too small, the append first moves the unread bytes to the front of the buffer (device
+ * to device, in pieces that never overlap their source) and counts their newlines again. */
+uint64_t sa_devtext_room(const sa_devtext *);
+/* host bytes to the write position; -3 (nothing done) when n > room, -1: call / device error */
+int sa_devtext_append(sa_devtext *, const uint8_t *bytes, uint64_t n);
+/* sa_inflate_members without the copy of the text to the host: the members' text lands at the
+ * devtext's write position back to back in list order (ms[i].out_off is not read, so any
+ * part of a scanned member list can be passed as it is).  The same host checks of in_off,
+ * in_len and isize, the same status array and return value as sa_inflate_members, and -3
+ * (nothing done) when the sum of the ISIZEs exceeds sa_devtext_room: pass fewer members.
+ * If any member fails or the call does, the write position does not move
+ * (unread text may have been moved to the front, which sa_devtext_peek / _cut do not see). */
+int sa_inflate_members_dev(sa_inflater *, const uint8_t *in, uint64_t in_bytes, const sa_bgzf_member *ms,
+                           uint32_t n, sa_devtext *dt, uint32_t *status);
+/* n bytes at read position + off to the host (the first line, the bare-'+' test) */
+int sa_devtext_peek(sa_devtext *, uint64_t off, uint8_t *out, uint64_t n);
+/* Cuts as many blocks as the unread text holds, at most max_blocks: block 0 starts at the
+ * read positions, each further one where the last ended; nothing is consumed.  t2 = NULL:
+ * single-end (len2 may be NULL).  eof: the devtext holds the rest of its input.  first / flen:
+ * input 1's first line, '\n' included (host memory).  The lengths are, block for block, what
+ * repeated sa_cut_next_se / sa_cut_next_pe return on the same bytes with the same avail and
+ * eof.  Returns the block count and in *end an SA_CUT_* value, or -1 for a call error. */
+int64_t sa_devtext_cut(sa_devtext *t1, int eof1, sa_devtext *t2, int eof2, uint64_t block_size,
+                       const uint8_t *first, uint64_t flen, uint64_t *len1, uint64_t *len2,
+                       uint64_t max_blocks, int32_t *end);
+/* One block's text copied device to device into an allocation of its own (from a pool of
+ * the device that sa_devblock_release gives it back to), the read positions advanced.
+ * t2 = NULL: single-end.  NULL on error (sa_devtext_error(t1)). */
+sa_devblock *sa_devtext_take(sa_devtext *t1, uint64_t len1, sa_devtext *t2, uint64_t len2);
+void sa_devblock_release(sa_devblock *);
+/* the block's text lengths; returns 1 for a paired block, 0 for single-end */
+int sa_devblock_lens(const sa_devblock *, uint64_t *len1, uint64_t *len2);
+/* the block's text to the host (out2 may be NULL); the command line needs it for block 0 only */
+int sa_devblock_fetch(const sa_devblock *, uint8_t *out1, uint8_t *out2);
+/* frees the device's pooled allocations that no devblock holds */
+void sa_devblock_pool_trim(int device);
+/* sa_text_upload with a device source: the devblock's text to block `index` of arena `slot`,
+ * device to device on the context's copy stream, done on return.  Then sa_text_parse.  A
+ * helper thread may call this while the context runs a batch, so its error text is kept apart
+ * from sa_last_error's, under the upload lock: sa_upload_error(ctx) after a non-zero return.
+ * (sa_text_upload is unchanged and still reports through sa_last_error.) */
+int sa_text_upload_dev(sa_ctx *ctx, sa_input *in, int slot, int index, int nmax, const sa_devblock *blk,
+                       uint64_t stride);
+const char *sa_upload_error(sa_ctx *ctx);   /* valid until the context's next sa_text_upload_dev */
+/* device time (ms, HIP events) of the devtext's last newline count and last cut (the cut is
+ * timed on the devtext passed as t1); either pointer may be NULL */
+void sa_devtext_kernel_ms(const sa_devtext *, float *count_ms, float *cut_ms);
+/* bytes the last newline count covered (with count_ms: the count's rate) */
+uint64_t sa_devtext_count_bytes(const sa_devtext *);
+
 #ifdef __cplusplus
 }
 #endif
