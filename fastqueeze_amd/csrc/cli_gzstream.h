@@ -576,8 +576,21 @@ struct GzStream : GzQueue {
                 const uint8_t* src = s->in.data() + m.in_off;
                 uint8_t* dst = s->out.data() + m.out_off;
                 bool bad = !ok;
-                if (ok && m.isize == 0) {   // (the BGZF end-of-file marker: an empty member)
-                    bad = m.crc != 0;
+                // An empty member (the BGZF end-of-file marker) is inflated like any other, into a
+                // one-byte dummy (its place in the slab's output may be no memory at all, and zlib
+                // refuses a null next_out): it is good only if its stream ends having produced no byte.
+                // A member with data behind a zeroed trailer produces one, or runs out of room.
+                uint8_t dummy = 0;
+                if (ok && m.isize == 0 && dd) {
+                    size_t got = 1;
+                    bad = ld.decompress(dd, src, m.in_len, &dummy, 1, &got) != 0 || got != 0 || m.crc != 0;
+                } else if (ok && m.isize == 0) {
+                    inflateReset(&z);
+                    z.next_in = const_cast<uint8_t*>(src);
+                    z.avail_in = (uInt)m.in_len;
+                    z.next_out = &dummy;
+                    z.avail_out = 1;
+                    bad = inflate(&z, Z_FINISH) != Z_STREAM_END || z.avail_out != 1 || m.crc != 0;
                 } else if (dd) {
                     size_t got = 0;
                     const int rc = ld.decompress(dd, src, m.in_len, dst, m.isize, &got);

@@ -23,6 +23,23 @@
 // end-of-block code, an over-subscribed set, and an incomplete set other than
 // a single one-bit code (no distance codes at all is allowed) are rejected; so
 // are the codes 286 / 287 and the distance codes 30 / 31 when they are used.
+// Each rule is pinned by a hand-built stream of tests/deflate_forge.py, on the
+// host emulation and on the device, with its status:
+//   HLIT > 286                      hlit_287, hlit_288
+//   HDIST > 30                      hdist_31, hdist_32
+//   a repeat without a previous     repeat_first
+//   a repeat past HLIT + HDIST      repeat_past_end, repeat_16_past_end
+//   a missing end-of-block code     no_end_of_block, hclen_4_all_zero
+//   an over-subscribed set          lit_oversubscribed, dist_oversubscribed, cl_oversubscribed
+//   an incomplete set               lit_incomplete, lit_one_2bit_code, dist_incomplete_two_2bit,
+//                                   dist_incomplete_one_2bit, cl_incomplete, dist_unused_code_used
+//   ... but one 1-bit code, or none dist_single_code0, dist_single_code29, dist_none, empty_dynamic (valid)
+//   the codes 286 / 287             fixed_litlen_286, fixed_litlen_287
+//   the distance codes 30 / 31      fixed_dist_30, fixed_dist_31
+// A member whose ISIZE is 0 is inflated like any other (isize0_dynamic_l9,
+// isize0_stored, isize0_fixed): with no room in the window its first byte is
+// SA_INFL_SIZE, so only a stream that ends having produced nothing is an empty
+// member.
 #pragma once
 #include <stddef.h>
 #include <stdint.h>

@@ -45,7 +45,11 @@ __global__ __launch_bounds__(64) void k_inflate_bgzf(const uint8_t* __restrict__
         const uint32_t in_len = ms[m].in_len, isize = ms[m].isize, crc = ms[m].crc;
         uint32_t st;
         if (isize == 0) {
-            st = crc ? (uint32_t)SA_INFL_CRC : (uint32_t)SA_INFL_OK;   // (the end-of-file marker)
+            // an empty member (the end-of-file marker) is inflated like any other: with no room in
+            // the window a literal, a match or a stored byte is SA_INFL_SIZE, so it is good only
+            // if its stream reaches the final end-of-block code having produced nothing
+            st = infl_member(in + in_off, in_len, infl_lds, 0, *tabs, lane, 64);
+            if (st == 0 && crc) st = SA_INFL_CRC;
         } else if (isize > INFL_MAX_ISIZE) {
             st = SA_INFL_SIZE;   // (the host rejects these before the launch)
         } else {

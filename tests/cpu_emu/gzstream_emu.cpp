@@ -56,11 +56,12 @@ static int inflate_members(sa_inflater* f, const uint8_t* in, uint64_t in_bytes,
         const sa_bgzf_member& m = ms[i];
         uint8_t* o = out + m.out_off;
         uint32_t crc = 0;
+        // (an empty member is inflated like any other: good only if its stream ends having produced nothing)
+        if (sa::infl_member(in + m.in_off, m.in_len, o, m.isize, f->tabs, 0, 1) != 0) {
+            failed++;
+            continue;
+        }
         if (m.isize) {
-            if (sa::infl_member(in + m.in_off, m.in_len, o, m.isize, f->tabs, 0, 1) != 0) {
-                failed++;
-                continue;
-            }
             uint32_t c = 0xffffffffu;
             for (uint32_t k = 0; k < m.isize; k++) c = f->crc_tab[(c ^ o[k]) & 0xffu] ^ (c >> 8);
             crc = ~c;

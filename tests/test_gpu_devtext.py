@@ -273,13 +273,16 @@ def test_cli_inputs_the_switch_cannot_take(cli_files):
 
 
 def test_cli_broken_input(cli_files):
-    """8. A BGZF file cut inside a member, junk after the last member and a wrong
-    CRC: a non-zero exit each, as on the host path, and no hang."""
+    """8. A BGZF file cut inside a member, junk after the last member, a wrong
+    CRC and a zeroed trailer: a non-zero exit each, as on the host path, and no hang."""
     d, z = cli_files
     ms, _, _ = fq.bgzf_scan(z)
     crc = bytearray(z)
     crc[int(ms[3]["in_off"]) + int(ms[3]["in_len"])] ^= 1
-    for name, data in (("cut", z[: len(z) * 2 // 3]), ("tail", z + b"\x1f\x8bjunk"), ("crc", bytes(crc))):
+    # member 3's trailer zeroed (a hole in the file): ISIZE 0 and CRC 0 in front of data is no empty member
+    end3 = int(ms[3]["in_off"]) + int(ms[3]["in_len"])
+    hole = z[:end3] + bytes(8) + z[end3 + 8:]
+    for name, data in (("cut", z[: len(z) * 2 // 3]), ("tail", z + b"\x1f\x8bjunk"), ("crc", bytes(crc)), ("hole", hole)):
         (d / f"{name}_1.fq.gz").write_bytes(data)
         for extra in ([], ["--gpu-text"]):
             r = subprocess.run([EXE, "-c", "-f", "--block-size", "1", "--batch", "4"] + extra +

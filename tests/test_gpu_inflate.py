@@ -173,10 +173,16 @@ def test_cli_gpu_inflate(tmp_path):
     z = bytearray(files["bgzf"][0])
     z[int(ms[3]["in_off"]) + int(ms[3]["in_len"])] ^= 1
     (tmp_path / "crc_1.fq").write_bytes(bytes(z))
-    for extra in ([], ["--gpu-inflate"]):
-        r = _run(["-c", "-f", "--ingest-only", "-t", "4"] + extra + ["-1", str(tmp_path / "crc_1.fq"), "-o",
-                                                                      str(tmp_path / "crc")], tmp_path)
-        assert r.returncode != 0, extra
+    # member 3's trailer zeroed (a hole in the file): ISIZE 0 and CRC 0 in front of data is no empty member
+    z = bytearray(files["bgzf"][0])
+    end3 = int(ms[3]["in_off"]) + int(ms[3]["in_len"])
+    z[end3:end3 + 8] = bytes(8)
+    (tmp_path / "hole_1.fq").write_bytes(bytes(z))
+    for k in ("crc", "hole"):
+        for extra in ([], ["--gpu-inflate"]):
+            r = _run(["-c", "-f", "--ingest-only", "-t", "4"] + extra + ["-1", str(tmp_path / f"{k}_1.fq"), "-o",
+                                                                          str(tmp_path / k)], tmp_path)
+            assert r.returncode != 0, (k, extra)
     # one-member plain gzip: the host path, said under -v, the same archive
     (tmp_path / "one_1.fq.gz").write_bytes(gzip.compress(synth.generate(6000, paired=False, seed=66)[0], 1))
     g0, _ = archive("one", tmp_path / "one_1.fq.gz", None, [])

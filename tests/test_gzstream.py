@@ -217,11 +217,15 @@ def _bad_files():
     assert sum(sizes[:bad_member]) > 3 * BGZF["slab"]
     flipped = bytearray(b)
     flipped[sum(sizes[:bad_member + 1]) - 8] ^= 1
+    # member 3's trailer zeroed (a hole in the file): ISIZE 0 and CRC 0 in front of 20,000 bytes of text
+    zeroed = bytearray(b)
+    zeroed[sum(sizes[:4]) - 8:sum(sizes[:4])] = bytes(8)
     z, tz = gz_files()["small_l6"]
     bgzf_modes = ("host", "dev-inflate")
     out = [("cut_in_member", b[:-(len(EOF_MEMBER) + 100)], bgzf_modes, t, len(t) - len(t) % MEMBER_TEXT),
            ("junk_after", b + b"\x1f\x8bjunk", bgzf_modes, t, len(t)),
            ("crc_flipped", bytes(flipped), bgzf_modes, t, bad_member * MEMBER_TEXT),
+           ("trailer_zeroed", bytes(zeroed), bgzf_modes + ("both",), t, 3 * MEMBER_TEXT),
            ("truncated", z[:len(z) * 2 // 3], ("host", "dev-gunzip"), tz, len(tz))]
     return out
 
@@ -236,6 +240,22 @@ def test_failures(emu, tmp_path):
     for name, data, modes, t, most in _bad_files():
         for mode in modes:
             _check_bad(emu["plain"], tmp_path, name, data, mode, t, most)
+
+
+def test_zeroed_trailer_is_an_error_not_an_empty_member(emu, tmp_path):
+    """A member with ISIZE 0 and CRC 0 is inflated like any other: with data in it
+    it fails on the host pool (libdeflate and zlib) and on the device path, and the
+    text before it is all that is delivered; the end-of-file marker, and one in
+    the middle of the file, are the only empty members that pass."""
+    name, data, _, t, most = [f for f in _bad_files() if f[0] == "trailer_zeroed"][0]
+    for mode, env in (("host", None), ("host", {"SA_NO_LIBDEFLATE": "1"}), ("dev-inflate", None), ("both", None)):
+        rc, word, text, log = run(emu["plain"], tmp_path, data, mode, env=env, tag=name)
+        assert (rc, word) == (1, "error"), (mode, env, word, log)
+        assert len(text) <= most and text == t[:len(text)], (mode, env, len(text))
+    sizes = member_sizes(small_bgzf())
+    eof_inside = small_bgzf()[:sum(sizes[:4])] + EOF_MEMBER + small_bgzf()[sum(sizes[:4]):]
+    for mode, env in (("host", None), ("host", {"SA_NO_LIBDEFLATE": "1"}), ("dev-inflate", None)):
+        assert ok_text(emu["plain"], tmp_path, eof_inside, mode, env=env, tag="eof_inside")[0] == small()
 
 
 def test_corrupt_gzip_on_the_device_path(emu, tmp_path):

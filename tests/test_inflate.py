@@ -220,6 +220,8 @@ def malformed():
     out.append(("match_first", w.done(), 3, 0, E_DIST))
     out.append(("isize_plus", cd3, len(d3) + 1, zlib.crc32(d3), E_SIZE))
     out.append(("isize_minus", cd3, len(d3) - 1, zlib.crc32(d3), E_SIZE))
+    # a zeroed trailer in front of data: an ISIZE 0 member is inflated too, and produces a byte it has no room for
+    out.append(("isize_zero", cd3, 0, 0, E_SIZE))
     out.append(("crc_wrong", cd3, len(d3), zlib.crc32(d3) ^ 0x8000, E_CRC))
     rng = np.random.default_rng(11)
     for name in ("fixed", "dynamic_l9", "full_flush_7000"):
