@@ -170,6 +170,7 @@ def load_library(path: str | None = None):
         "sa_devblock_pool_trim": ([I32], None),
         "sa_text_upload_dev": ([P, P, I32, I32, I32, P, U64], I32), "sa_upload_error": ([P], C.c_char_p),
         "sa_devtext_kernel_ms": ([P, P, P], None), "sa_devtext_count_bytes": ([P], U64),
+        "sa_gunzip_run_dev": ([P, P, U64, I32, P, P, U64, P, P, P], I32),
     }
     for name, (args, res) in sigs.items():
         fn = getattr(lib, name)
@@ -911,6 +912,50 @@ class Gunzipper:
                 raise SeqArcError(f"the device path makes too little progress (end_why {self.last_info['end_why']}): "
                                   "inflate this stream on the host")
         return b"".join(parts)
+
+    def run_to(self, devtext: "DevText", data, state: GunzipState, eof: bool = True, out_cap: int | None = None):
+        """One sa_gunzip_run_dev: the confirmed prefix's text appended to the devtext,
+        never on the host; (return value, text_bytes, in_used).  out_cap (default: the
+        devtext's room) is the most text the call may append; -3: it exceeds devtext.room
+        (nothing done).  Any other negative return value raises."""
+        a = _as_u8(data)
+        tb, used, info = C.c_uint64(0), C.c_uint64(0), GunzipInfo()
+        rc = self._lib.sa_gunzip_run_dev(self._h, _ptr(a), a.size, int(eof), C.byref(state), devtext._h,
+                                         devtext.room if out_cap is None else out_cap, C.byref(tb), C.byref(used),
+                                         C.byref(info))
+        self.last_info = info.as_dict()
+        if rc < 0 and rc != -3:
+            raise SeqArcError(f"sa_gunzip_run_dev ({rc}): {self._lib.sa_gunzipper_error(self._h).decode()}")
+        return rc, tb.value, used.value
+
+    def gunzip_to(self, devtext: "DevText", data, slab: int | None = None, out_cap: int | None = None) -> int:
+        """A whole gzip file's text appended to the devtext: gunzip()'s loop over
+        sa_gunzip_run_dev, each call with the devtext's room (at most out_cap) for its
+        text.  Returns the text bytes appended; raises where gunzip() raises, and when
+        the devtext has no room left."""
+        a = _as_u8(data)
+        slab = slab or self.SLAB
+        state = GunzipState()
+        total, at, carry = 0, 0, np.zeros(0, np.uint8)
+        self.calls = []
+        while True:
+            take = min(slab, a.size - at)
+            buf = np.concatenate([carry, a[at:at + take]]) if carry.size else a[at:at + take]
+            at += take
+            eof = at == a.size
+            rc, tb, used = self.run_to(devtext, buf, state, eof, min(out_cap or devtext.room, devtext.room))
+            self.calls.append(self.last_info)
+            total += tb
+            if rc > 0:
+                raise SeqArcError(f"gzip stream is corrupt: status {rc} ({INFLATE_STATUS.get(rc, '?')}) after "
+                                  f"{total} text bytes")
+            carry = buf[used:]
+            if state.ended or (eof and carry.size == 0):
+                break
+            if (self.last_info["chunks"] >= 2 and used < self.chunk) or (eof and not used and not tb):
+                raise SeqArcError(f"the device path makes too little progress (end_why {self.last_info['end_why']}): "
+                                  "inflate this stream on the host")
+        return total
 
 
 class Input:

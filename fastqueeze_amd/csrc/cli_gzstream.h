@@ -18,6 +18,8 @@
 // fills one of two page-locked output slabs while a copier thread copies the
 // other into the queue's chunk).  Their device calls go through GzDevice, so
 // that tests/cpu_emu/gzstream_emu.cpp drives all of this without the library.
+// What a gunzip loop does after a call is gz_after_call, which --gpu-text's
+// gzip input (cli_devinput.h) follows too.
 #pragma once
 #include <dlfcn.h>
 #include <errno.h>
@@ -393,6 +395,32 @@ struct OutPair {
         return cgone;
     }
 };
+
+// What a --gpu-gunzip loop does after a call that returned 0 (run_plain_gpu, and
+// cli_devinput.h's gzip input).  left: the input bytes the call did not consume;
+// last: the slab is the file's last; room: the bytes a slab has in front for a
+// carry; text_bytes: the text the call delivered.
+//   Over      the stream is over
+//   Leave     the device path ends and the host continues from the state: a call
+//             of two chunks or more that confirmed less than one, a last slab
+//             without any progress, one wave confirmed in a call of four chunks
+//             or more (the stream has no block starts to find -- stored or fixed
+//             blocks only -- and one wave would go on doing all the work), or
+//             more left than the next slab has room for
+//   Again     another call on what is left (the last slab's rest runs alone)
+//   NextSlab  what is left goes in front of the next slab
+enum class GzAfter { Over, Leave, Again, NextSlab };
+inline GzAfter gz_after_call(const sa_gunzip_info& info, const sa_gunzip_state& gs, uint64_t in_used, uint64_t text_bytes,
+                             uint64_t left, bool last, uint64_t chunk, uint64_t room)
+{
+    if (gs.ended || (last && left == 0)) return GzAfter::Over;
+    const bool low = (info.chunks >= 2 && in_used < chunk) || (last && !in_used && !text_bytes) ||
+                     (info.chunks >= 4 && info.waves_confirmed == 1 && info.end_why != SA_GZ_OUTCAP);
+    if (low || (!last && left > room)) return GzAfter::Leave;
+    if (!last && (info.end_why != SA_GZ_OUTCAP && info.end_why != SA_GZ_BREAKS && info.end_why != SA_GZ_FULL)) return GzAfter::NextSlab;
+    if (!last && left < chunk) return GzAfter::NextSlab;
+    return GzAfter::Again;
+}
 
 struct GzStream : GzQueue {
     int fd = -1;
@@ -910,15 +938,12 @@ struct GzStream : GzQueue {
                     in += in_used;
                     n -= in_used;
                     in_at += in_used;
-                    if (gs->ended || (s->last && n == 0)) {
+                    const GzAfter next = gz_after_call(info, *gs, in_used, out_bytes, n, s->last, chunk, gunzip_room);
+                    if (next == GzAfter::Over) {
                         over = true;
                         break;
                     }
-                    // (one wave confirmed in a call of four chunks or more: the stream has no block starts
-                    // to find -- stored or fixed blocks only -- and one wave would go on doing all the work)
-                    const bool low = (info.chunks >= 2 && in_used < chunk) || (s->last && !in_used && !out_bytes) ||
-                                     (info.chunks >= 4 && info.waves_confirmed == 1 && info.end_why != SA_GZ_OUTCAP);
-                    if (low || (!s->last && n > gunzip_room)) {
+                    if (next == GzAfter::Leave) {
                         leave = true;
                         host_at = in_at;
                         if (verbose)
@@ -929,9 +954,7 @@ struct GzStream : GzQueue {
                                     (unsigned long long)host_at);
                         break;
                     }
-                    // the next slab goes behind what is left, unless this is the last: then what is left runs alone
-                    if (!s->last && (info.end_why != SA_GZ_OUTCAP && info.end_why != SA_GZ_BREAKS && info.end_why != SA_GZ_FULL)) break;
-                    if (!s->last && n < chunk) break;
+                    if (next == GzAfter::NextSlab) break;   // the next slab goes behind what is left
                 }
                 if (!fail && !gone && !leave && !over) carry.assign(in, in + n);
                 feed.retire(fail, gone || over, leave);

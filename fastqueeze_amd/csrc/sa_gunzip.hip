@@ -1,5 +1,7 @@
-// sa_gunzip.hip -- ordinary gzip inflated on the device (sa_gunzip_run).
-// Included by sa_engine.hip (needs DBuf).
+// sa_gunzip.hip -- ordinary gzip inflated on the device (sa_gunzip_run, and
+// sa_gunzip_run_dev: the text into a devtext and never to the host).
+// Included by sa_engine.hip after sa_devtext.hip (needs DBuf, sa_devtext,
+// dt_make_room and dt_count).
 //
 // The stages of sa_gunzip.h as separate launches on one stream; NO kernel waits
 // for another wave -- no spin, no flag polling, no cooperative launch: what a
@@ -203,9 +205,18 @@ namespace {
         }                                                                \
     } while (0)
 
-// gz_run's backend: the stages as kernels on the gunzipper's stream
+// gz_run's backend: the stages as kernels on the gunzipper's stream.  With a
+// sink (sa_gunzip_run_dev) the text is resolved into the devtext at its write
+// position and summed there, and never copied to the host.  The kernels get the
+// devtext's base, which is 16-byte aligned (k_gz_crc's vector loads rely on it),
+// and the write position is added to the offsets here: to the confirmed waves'
+// (d_woff, which the chain wrote and the host has read) and to a copy of the
+// CRC tasks.
 struct GzDevice {
     sa_gunzipper& g;
+    sa_devtext* sink = nullptr;
+    std::vector<uint64_t> sink_woff;
+    std::vector<GzAccount::Task> sink_tasks;
     uint32_t in_len = 0, nw = 0, nconf = 0, ntasks = 0;
     const sa_gunzip_state* state = nullptr;
     uint32_t h_bad = 0;
@@ -299,20 +310,37 @@ struct GzDevice {
         wwl.resize(nconf);
         return true;
     }
-    bool resolve(const GzPlan&, const std::vector<uint32_t>&, const std::vector<uint64_t>&, const std::vector<uint32_t>&,
-                 const std::vector<GzWaveRes>&, uint8_t* out, uint64_t text)
+    bool resolve(const GzPlan&, const std::vector<uint32_t>& order, const std::vector<uint64_t>& woff, const std::vector<uint32_t>&,
+                 const std::vector<GzWaveRes>& res, uint8_t* out, uint64_t text)
     {
-        GZ_CHECK(g.d_text.ensure(text + 16));
+        uint8_t* d_text = nullptr;
+        if (sink) {
+            // (the caller made room for out_cap >= text bytes behind wr; a wave outside [0, text) would write
+            // outside them)
+            sink_woff.resize(nconf);
+            for (uint32_t k = 0; k < nconf; k++) {
+                if (order[k] >= nw || woff[k] > text || res[order[k]].lb_sym > text - woff[k] || sink->wr + text > sink->cap) {
+                    g.err = "sa_gunzip_run_dev: a confirmed wave's text lies outside the call's";
+                    return false;
+                }
+                sink_woff[k] = sink->wr + woff[k];
+            }
+            GZ_CHECK(hipMemcpyAsync(g.d_woff.p, sink_woff.data(), 8ull * nconf, hipMemcpyHostToDevice, g.st));
+            d_text = sink->buf;
+        } else {
+            GZ_CHECK(g.d_text.ensure(text + 16));
+            d_text = g.d_text.as<uint8_t>();
+        }
         GZ_CHECK(g.d_bad.ensure(4));
         GZ_CHECK(hipMemsetAsync(g.d_bad.p, 0, 4, g.st));
         GZ_CHECK(hipEventRecord(g.ev[6], g.st));
         hipLaunchKernelGGL(k_gz_resolve, dim3(64, nconf), dim3(256), 0, g.st, g.d_order.as<uint32_t>(), g.d_woff.as<uint64_t>(),
                            g.d_wwl.as<uint32_t>(), g.d_res.as<GzWaveRes>(), g.d_base.as<uint64_t>(), g.d_sym.as<uint16_t>(),
-                           g.d_win.as<uint8_t>(), g.d_text.as<uint8_t>(), g.d_bad.as<uint32_t>());
+                           g.d_win.as<uint8_t>(), d_text, g.d_bad.as<uint32_t>());
         GZ_CHECK(hipGetLastError());
         GZ_CHECK(hipEventRecord(g.ev[7], g.st));
         GZ_CHECK(hipMemcpyAsync(&h_bad, g.d_bad.p, 4, hipMemcpyDeviceToHost, g.st));
-        if (text) GZ_CHECK(hipMemcpyAsync(out, g.d_text.p, text, hipMemcpyDeviceToHost, g.st));
+        if (text && !sink) GZ_CHECK(hipMemcpyAsync(out, g.d_text.p, text, hipMemcpyDeviceToHost, g.st));
         ran[3] = true;
         return true;
     }
@@ -322,11 +350,17 @@ struct GzDevice {
         if (!ntasks) return true;
         GZ_CHECK(g.d_tasks.ensure(sizeof(GzAccount::Task) * (size_t)ntasks));
         GZ_CHECK(g.d_crcs.ensure(4ull * ntasks));
-        GZ_CHECK(hipMemcpyAsync(g.d_tasks.p, tasks.data(), sizeof(GzAccount::Task) * (size_t)ntasks, hipMemcpyHostToDevice, g.st));
+        const GzAccount::Task* h_tasks = tasks.data();
+        if (sink) {
+            sink_tasks = tasks;
+            for (GzAccount::Task& t : sink_tasks) t.off += sink->wr;
+            h_tasks = sink_tasks.data();
+        }
+        GZ_CHECK(hipMemcpyAsync(g.d_tasks.p, h_tasks, sizeof(GzAccount::Task) * (size_t)ntasks, hipMemcpyHostToDevice, g.st));
         GZ_CHECK(hipMemsetAsync(g.d_counter.p, 0, 4, g.st));
         GZ_CHECK(hipEventRecord(g.ev[8], g.st));
-        hipLaunchKernelGGL(k_gz_crc, dim3(std::min(g.grid, ntasks)), dim3(64), GZ_CRC_LDS, g.st, g.d_text.as<uint8_t>(),
-                           g.d_tasks.as<GzAccount::Task>(), ntasks, g.d_crcs.as<uint32_t>(), g.d_counter.as<uint32_t>());
+        hipLaunchKernelGGL(k_gz_crc, dim3(std::min(g.grid, ntasks)), dim3(64), GZ_CRC_LDS, g.st,
+                           sink ? sink->buf : g.d_text.as<uint8_t>(), g.d_tasks.as<GzAccount::Task>(), ntasks, g.d_crcs.as<uint32_t>(), g.d_counter.as<uint32_t>());
         GZ_CHECK(hipGetLastError());
         GZ_CHECK(hipEventRecord(g.ev[9], g.st));
         GZ_CHECK(hipMemcpyAsync(crcs.data(), g.d_crcs.p, 4ull * ntasks, hipMemcpyDeviceToHost, g.st));
@@ -415,6 +449,47 @@ int sa_gunzip_run(sa_gunzipper* g, const uint8_t* in, uint64_t in_bytes, int eof
     }
     GzDevice be{*g};
     return gz_run(be, in, in_bytes, eof, state, out, out_cap, out_bytes, in_used, info, g->chunk, g->ratio, g->err);
+}
+
+// The gunzipper's kernels run on its stream and the devtext's move and count on
+// the devtext's.  No event orders the two: dt_make_room and dt_count return
+// synchronised, and so does gz_run (finish), so each step finds the other
+// stream idle -- sa_inflate_members_dev's arrangement.
+int sa_gunzip_run_dev(sa_gunzipper* g, const uint8_t* in, uint64_t in_bytes, int eof, sa_gunzip_state* state, sa_devtext* dt,
+                      uint64_t out_cap, uint64_t* text_bytes, uint64_t* in_used, sa_gunzip_info* info)
+{
+    if (!g) return -1;
+    g->err.clear();
+    g->kernel_ms = 0.f;
+    if (text_bytes) *text_bytes = 0;
+    if (!state || !text_bytes || !in_used || (in_bytes && !in) || !dt || dt->device != g->device) {
+        g->err = "sa_gunzip_run_dev: null argument, or a devtext of another device";
+        return -1;
+    }
+    if (out_cap > sa_devtext_room(dt)) {
+        g->err = "sa_gunzip_run_dev: out_cap exceeds sa_devtext_room";
+        return -3;
+    }
+    dt->err.clear();
+    if (hipSetDevice(g->device) != hipSuccess) {
+        g->err = "sa_gunzip_run_dev: hipSetDevice failed";
+        return -1;
+    }
+    if (dt_make_room(dt, out_cap)) {
+        g->err = "sa_gunzip_run_dev: " + dt->err;
+        return -1;
+    }
+    GzDevice be{*g, dt};
+    uint64_t text = 0;
+    const int rc = gz_run(be, in, in_bytes, eof, state, nullptr, out_cap, &text, in_used, info, g->chunk, g->ratio, g->err);
+    if (rc != 0) return rc;   // (bytes behind the write position are scratch: it does not move)
+    if (dt_count(dt, dt->wr, dt->wr + text)) {
+        g->err = "sa_gunzip_run_dev: " + dt->err;
+        return -1;
+    }
+    dt->wr += text;
+    *text_bytes = text;
+    return 0;
 }
 
 }  // extern "C"

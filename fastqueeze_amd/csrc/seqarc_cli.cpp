@@ -31,7 +31,8 @@
 //                    (sa_devtext; one device, device parse; off by default)
 //                    instead of on host threads; other gzip files keep the host path
 //   --gpu-gunzip     gzip inputs that are not BGZF (gzip, pigz, concatenated members) are
-//                    inflated on the first device by speculation (sa_gunzip_run)
+//                    inflated on the first device by speculation (sa_gunzip_run); with
+//                    --gpu-text their text stays on the device too (sa_gunzip_run_dev)
 //
 // Compression mirrors SeqArc-1.6 main@0x41fd40 -> SeqArcContext::doReadAndEncode
 // @0x41a4e0 as a stream: one reader thread cuts 50 MiB blocks as the input
@@ -75,6 +76,7 @@
 #include <vector>
 
 #include "../../include/seqarc_amd.h"
+#include "cli_devinput.h"
 #include "cli_gzstream.h"
 #include "cli_knobs.h"
 #include "cli_plan.h"
@@ -96,7 +98,8 @@ int usage()
             "       (--gpu-inflate: BGZF inputs of -c are inflated on the first device, not on host threads)\n"
             "       (--gpu-text: BGZF inputs of -c are inflated, cut into blocks and parsed on the device, the text\n"
             "        never on the host; not with --ingest-only, --host-only, --host-parse, --stage-ahead)\n"
-            "       (--gpu-gunzip: gzip inputs of -c that are not BGZF are inflated on the first device)\n");
+            "       (--gpu-gunzip: gzip inputs of -c that are not BGZF are inflated on the first device; with\n"
+            "        --gpu-text their text stays on the device as well)\n");
     return 2;
 }
 
@@ -411,141 +414,21 @@ bool is_bgzf_file(const char* path)
            h[13] == 'C' && h[14] == 2 && h[15] == 0;
 }
 
-// --gpu-text: one BGZF input inflated into a devtext (sa_devtext), where the
-// block cut finds it.  The compressed side is --gpu-inflate's: a file thread
-// reads slabs of whole members (GzStream::BgzfReader: the carry, the member
-// walk, its three errors) and publishes them through a SlabFeed.  There is no
-// output side: the reader thread of the pipeline (read_device) takes the
-// oldest slab and calls sa_inflate_members_dev with as many of its members as
-// the devtext has room for -- one thread drives the devtext.
-struct DevInput {
-    struct Slab {
-        uint8_t* in = nullptr;   // sa_host_alloc, slab_bytes
-        std::vector<sa_bgzf_member> ms;
-    };
-    static constexpr uint64_t kCapacity = 1ull << 30;   // the devtext's bytes (per mate)
-    static constexpr uint64_t kCall = 256ull << 20;     // text bytes of one device call at most
-    GzStream gz{kGzDevice};   // never started: the BgzfReader's view of the file (fd, slab_bytes, readn)
-    SlabFeed<Slab> feed{kGzDevice, 4};
-    sa_inflater* infl = nullptr;
-    sa_devtext* dt = nullptr;
-    std::string name;
-    bool file_bad = false;   // (under feed.pm) the file thread ended on an error
-    // ---- the reader thread's ----
-    Slab* cur = nullptr;     // the slab being inflated and its next member
-    size_t at = 0;
-    bool eof = false, started = false, closed = false;
-    std::vector<sa_bgzf_member> grp;
-    uint64_t members = 0, text_bytes = 0, calls = 0;   // (-v)
-    double kernel_ms = 0, count_ms = 0, call_ms = 0;
+// the file starts with a gzip member header
+bool is_gzip_file(const char* path)
+{
+    const int fd = ::open(path, O_RDONLY);
+    if (fd < 0) return false;
+    uint8_t m[2] = {0, 0};
+    const ssize_t r = ::pread(fd, m, 2, 0);
+    ::close(fd);
+    return r == 2 && m[0] == 0x1f && m[1] == 0x8b;
+}
 
-    bool start(int fd, const char* path, int device, std::string& err)
-    {
-        name = path;
-        gz.fd = fd;
-        gz.name = path;
-        infl = sa_inflater_create(device);
-        dt = infl ? sa_devtext_create(device, kCapacity) : nullptr;
-        if (!infl || !dt) {
-            err = "--gpu-text: no usable gfx950 device " + std::to_string(device) + ", or no device memory for the text";
-            return false;
-        }
-        feed.device = std::thread([this]() {   // (SlabFeed joins it in finish(); here it is the file's reader)
-            lower_priority();
-            GzStream::BgzfReader rd{gz};
-            bool ok = true;
-            while (rd.more()) {
-                std::unique_ptr<Slab> s(new Slab());
-                s->in = feed.get(gz.slab_bytes);
-                if (!s->in) break;   // (the pipeline's reader stopped, or no memory: feed.bad)
-                uint64_t total = 0;
-                // (a member of more than 65,536 text bytes is an error: the kernel's window holds no more)
-                const int got = rd.next(s->in, s->ms, total, sa::INFL_MAX_ISIZE);
-                if (got <= 0) {
-                    feed.put_back(s->in);
-                    ok = got == 0;
-                    break;
-                }
-                feed.publish(std::move(s));
-            }
-            {   // the end: the slabs still queued are taken, then next() gives nullptr
-                std::lock_guard<std::mutex> g(feed.pm);
-                file_bad = !ok || feed.bad;
-                feed.quit = true;
-            }
-            feed.pcv.notify_all();
-        });
-        started = true;
-        return true;
-    }
-    // inflates into the devtext until it holds `want` bytes or the input is used up; false: err
-    bool pump(uint64_t want, std::string& err)
-    {
-        while (!eof && sa_devtext_avail(dt) < want) {
-            if (!cur) {
-                cur = feed.next();
-                at = 0;
-                if (!cur) {
-                    std::lock_guard<std::mutex> g(feed.pm);
-                    if (file_bad) {
-                        err = "read error on " + name + " (not BGZF throughout, a member cut short, or bytes after the last member)";
-                        return false;
-                    }
-                    eof = true;
-                    break;
-                }
-            }
-            // members [at, b): what the devtext has room for, at most kCall text bytes
-            const uint64_t room = std::min<uint64_t>(sa_devtext_room(dt), kCall);
-            size_t b = at;
-            uint64_t total = 0;
-            while (b < cur->ms.size() && total + cur->ms[b].isize <= room) total += cur->ms[b++].isize;
-            if (b == at) {   // (want is far below the capacity: a devtext short of it has room for a member)
-                err = "--gpu-text: the device text of " + name + " has no room for a member";
-                return false;
-            }
-            const uint64_t in0 = cur->ms[at].in_off, in1 = cur->ms[b - 1].in_off + cur->ms[b - 1].in_len;
-            grp.assign(cur->ms.begin() + (std::ptrdiff_t)at, cur->ms.begin() + (std::ptrdiff_t)b);
-            for (sa_bgzf_member& m : grp) m.in_off -= in0;
-            const auto t0 = gz_now();
-            const int rc = sa_inflate_members_dev(infl, cur->in + in0, in1 - in0, grp.data(), (uint32_t)grp.size(), dt, nullptr);
-            if (rc != 0) {   // (> 0: members that do not inflate or whose CRC differs -- the host path's error)
-                err = rc < 0 ? std::string("--gpu-text: ") + sa_inflater_error(infl) : "read error on " + name + " (a BGZF member does not inflate, or its CRC differs)";
-                return false;
-            }
-            call_ms += gz_ms_since(t0);
-            kernel_ms += sa_inflater_kernel_ms(infl);
-            float cms = 0;
-            sa_devtext_kernel_ms(dt, &cms, nullptr);
-            count_ms += cms;
-            members += grp.size();
-            text_bytes += total;
-            calls++;
-            at = b;
-            if (at == cur->ms.size()) {
-                feed.retire(false, false, false);
-                cur = nullptr;
-            }
-        }
-        return true;
-    }
-    // the reader thread, on every way out: the file thread ended and joined, the slabs freed
-    void close()
-    {
-        if (!started || closed) return;
-        closed = true;
-        if (cur) feed.retire(false, true, false);
-        else feed.reader_gone();
-        cur = nullptr;
-        feed.finish();
-    }
-    ~DevInput()
-    {
-        close();
-        if (infl) sa_inflater_destroy(infl);
-        if (dt) sa_devtext_destroy(dt);
-    }
-};
+// --gpu-text: a compressed input inflated into a devtext (DevInput, cli_devinput.h);
+// its devtext calls go through this table.
+const DevTextCalls kDevTextCalls = {sa_devtext_create, sa_devtext_destroy,   sa_devtext_avail,       sa_devtext_room, sa_devtext_append,
+                                    sa_devtext_error,  sa_devtext_kernel_ms, sa_inflate_members_dev, sa_gunzip_run_dev};
 
 // Newlines in t[0, len): 64 bytes a step (compare, movemask, popcount).
 uint64_t count_newlines(const uint8_t* t, uint64_t len)
@@ -1572,7 +1455,7 @@ struct Pipeline {
     const bool pe;
     Stamps st;
     Input in1, in2;
-    // --gpu-text applies: the inputs are BGZF and their text lives in these (read_device)
+    // --gpu-text applies: the inputs are BGZF (or, with --gpu-gunzip, gzip) and their text lives in these (read_device)
     bool dev_text = false;
     std::unique_ptr<DevInput> dv1, dv2;
     std::string path;
@@ -1643,13 +1526,17 @@ struct Pipeline {
                 return false;
             }
         }
-        // --gpu-text takes BGZF inputs on one device; anything else runs as it would without the switch
+        // --gpu-text takes BGZF inputs, and with --gpu-gunzip other gzip inputs, in any mix, on one device;
+        // anything else runs as it would without the switch
         if (o.gpu_text) {
-            const bool bgzf = is_bgzf_file(o.f1) && (!pe || is_bgzf_file(o.f2));
-            dev_text = bgzf && o.devices == 1;
+            auto takes = [&](const char* f) { return is_bgzf_file(f) || (o.gpu_gunzip && is_gzip_file(f)); };
+            const bool all = takes(o.f1) && (!pe || takes(o.f2));
+            dev_text = all && o.devices == 1;
             if (!dev_text && o.verbose)
                 fprintf(stderr, "seqarc_amd: --gpu-text does not apply (%s): running without it\n",
-                        !bgzf ? "an input is not BGZF" : "more than one device");
+                        all           ? "more than one device"
+                        : o.gpu_gunzip ? "an input is neither BGZF nor gzip"
+                                       : "an input is not BGZF");
         }
         if (!in1.open(o.f1, dev_text) || (pe && !in2.open(o.f2, dev_text))) {
             fprintf(stderr, "seqarc_amd: cannot open the input\n");
@@ -1943,8 +1830,9 @@ struct Pipeline {
         }
     }
 
-    // --gpu-text: BGZF inputs whose text stays on the device.  Each mate's
-    // devtext is pumped to a cut window (DevInput::pump: sa_inflate_members_dev),
+    // --gpu-text: compressed inputs whose text stays on the device.  Each mate's
+    // devtext is pumped to a cut window (DevInput::pump: sa_inflate_members_dev
+    // for BGZF, sa_gunzip_run_dev for other gzip),
     // sa_devtext_cut cuts every block the text holds, and each block leaves as a
     // devblock in its Job -- the encoders upload it device to device (upload).
     // Block 0 is also fetched to the host: the parser needs it for the ID template.
@@ -1961,19 +1849,16 @@ struct Pipeline {
             for (DevInput* d : {dv1.get(), dv2.get()}) {
                 if (!d) continue;
                 d->close();
-                if (o.verbose)
-                    fprintf(stderr,
-                            "seqarc_amd: --gpu-text: %s: %llu member(s), %llu text bytes in %llu call(s) on device %d: "
-                            "sa_inflate_members_dev %.3f s (inflate kernel %.3f s, newline count %.1f ms); cut %.1f ms over "
-                            "%lld blocks in %llu call(s); waited %.3f s for room\n",
-                            d->name.c_str(), (unsigned long long)d->members, (unsigned long long)d->text_bytes,
-                            (unsigned long long)d->calls, o.device, d->call_ms / 1e3, d->kernel_ms / 1e3, d->count_ms, cut_ms,
-                            (long long)nread_local, (unsigned long long)cuts, room_wait);
+                if (o.verbose) d->say(cut_ms, (long long)nread_local, (unsigned long long)cuts, room_wait);
             }
         };
-        dv1.reset(new DevInput());
-        if (pe) dv2.reset(new DevInput());
-        if (!dv1->start(in1.fd, o.f1, o.device, e) || (pe && !dv2->start(in2.fd, o.f2, o.device, e))) return done(), fail(e);
+        dv1.reset(new DevInput(kGzDevice, kDevTextCalls));
+        if (pe) dv2.reset(new DevInput(kGzDevice, kDevTextCalls));
+        for (DevInput* d : {dv1.get(), dv2.get()})
+            if (d) d->gz.verbose = o.verbose;
+        auto kind = [](const char* f) { return is_bgzf_file(f) ? DevInput::BGZF : DevInput::GZIP; };
+        if (!dv1->start(in1.fd, o.f1, o.device, kind(o.f1), e) || (pe && !dv2->start(in2.fd, o.f2, o.device, kind(o.f2), e)))
+            return done(), fail(e);
         for (int64_t i = 0;;) {
             const double tf0 = st.now();
             const uint64_t had = sa_devtext_avail(dv1->dt) + (pe ? sa_devtext_avail(dv2->dt) : 0);

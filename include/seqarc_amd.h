@@ -523,7 +523,8 @@ uint32_t sa_gunzipper_chunk(const sa_gunzipper *);     /* bytes per chunk in eff
 /* ---- text resident on the device: sa_devtext --------------------------------
  * One input's FASTQ text as a stream in device memory: a linear buffer with a read and a
  * write position and a stream of its own; no sa_ctx needed.  Text arrives by sa_devtext_append
- * (from the host) or sa_inflate_members_dev (BGZF members inflated straight into it), the block
+ * (from the host), sa_inflate_members_dev (BGZF members inflated straight into it) or
+ * sa_gunzip_run_dev (ordinary gzip, by speculation, straight into it), the block
  * cut of sa_cut_next_se / sa_cut_next_pe runs on the device (sa_devtext_cut, k_dt_cut), a block
  * leaves as a sa_devblock, made by sa_devtext_take, and reaches an encoder's text arena by
  * sa_text_upload_dev; sa_text_parse then works as after sa_text_upload.  The text never
@@ -559,6 +560,21 @@ int sa_devtext_append(sa_devtext *, const uint8_t *bytes, uint64_t n);
  * (unread text may have been moved to the front, which sa_devtext_peek / _cut do not see). */
 int sa_inflate_members_dev(sa_inflater *, const uint8_t *in, uint64_t in_bytes, const sa_bgzf_member *ms,
                            uint32_t n, sa_devtext *dt, uint32_t *status);
+/* sa_gunzip_run without the copy of the text to the host: the confirmed prefix's text lands at
+ * the devtext's write position (the devtext must be on the gunzipper's device).  out_cap is the
+ * most text the call may deliver: -3 (nothing done) when it exceeds sa_devtext_room; otherwise
+ * room for out_cap bytes is made behind the write position first, as an append does (unread
+ * text may move to the front).  0: *text_bytes bytes were appended and counted, and *in_used,
+ * *state and *info are sa_gunzip_run's.  Any other return value -- > 0: the stream is corrupt
+ * (SA_INFL_*), < 0: a call error (-2: out_cap is too small for the first wave) -- leaves the
+ * write position where it was and *text_bytes = 0; no byte below the write position is written,
+ * the bytes behind it are scratch.  Unlike sa_gunzip_run this call does not deliver the text
+ * before an error, and *state after a positive return is not one to continue from: the input
+ * has failed.  The 256 MiB input limit and sa_gunzipper_kernel_ms are sa_gunzip_run's;
+ * sa_gunzipper_error carries the devtext's error text when the devtext failed. */
+int sa_gunzip_run_dev(sa_gunzipper *, const uint8_t *in, uint64_t in_bytes, int eof, sa_gunzip_state *state,
+                      sa_devtext *dt, uint64_t out_cap, uint64_t *text_bytes, uint64_t *in_used,
+                      sa_gunzip_info *info);
 /* n bytes at read position + off to the host (the first line, the bare-'+' test) */
 int sa_devtext_peek(sa_devtext *, uint64_t off, uint8_t *out, uint64_t n);
 /* Cuts as many blocks as the unread text holds, at most max_blocks: block 0 starts at the
