@@ -23,7 +23,7 @@ from . import build as _build
 
 __all__ = ["SeqArcError", "blocks_from_fastq", "Block", "Config", "Encoder", "cut_se", "cut_pe", "parse_se", "parse_pe", "analyze_ids",
            "load_library", "BLOCK_SIZE", "Input", "bgzf_scan", "Inflater", "BGZF_MEMBER", "INFLATE_STATUS",
-           "Gunzipper", "GunzipState", "GunzipInfo"]
+           "Gunzipper", "GunzipState", "GunzipInfo", "Decoder", "DecodeInfo"]
 
 BLOCK_SIZE = 50 << 20   # SeqArcParam BlockSize(M) = 50 (ctor @0x40776f)
 
@@ -171,6 +171,8 @@ def load_library(path: str | None = None):
         "sa_text_upload_dev": ([P, P, I32, I32, I32, P, U64], I32), "sa_upload_error": ([P], C.c_char_p),
         "sa_devtext_kernel_ms": ([P, P, P], None), "sa_devtext_count_bytes": ([P], U64),
         "sa_gunzip_run_dev": ([P, P, U64, I32, P, P, U64, P, P, P], I32),
+        "sa_decoder_create": ([I32], P), "sa_decoder_destroy": ([P], None), "sa_decoder_error": ([P], C.c_char_p),
+        "sa_decode_blocks": ([P, P, P, P, C.c_uint32, P, P, I32, P, P], I32), "sa_decoder_info": ([P, P], None),
     }
     for name, (args, res) in sigs.items():
         fn = getattr(lib, name)
@@ -1054,6 +1056,86 @@ def decode_block(data: bytes, text_bytes: int, cfg: Config | None = None, templa
     ln, ls = int(nl[:n].astype(np.int64).sum()), int(sl[:n].astype(np.int64).sum())
     return Block(names[:ln].copy(), nl[:n].copy(), seq[:ls].copy(), sl[:n].copy(), qual[:ls].copy(), text_bytes), \
         bool(d.md5_ok)
+
+
+class DecodeInfo(C.Structure):
+    """sa_decode_info: what the last sa_decode_blocks call did."""
+    _fields_ = [("groups", C.c_uint32), ("inflight", C.c_uint32), ("slice", C.c_uint32), ("qual_launches", C.c_uint32),
+                ("seq_launches", C.c_uint32), ("unsupported", C.c_uint32), ("init_ms", C.c_float), ("qual_ms", C.c_float),
+                ("place_ms", C.c_float), ("seq_ms", C.c_float), ("h2d_ms", C.c_float), ("d2h_ms", C.c_float)]
+
+
+# why a block's decode ended (SA_DEC_* of include/seqarc_amd.h)
+DEC_OK, DEC_LAYOUT, DEC_INPUT, DEC_SLOT, DEC_RANGE, DEC_PLACE, DEC_UNSUPPORTED, DEC_STUCK = range(8)
+
+
+class Decoder:
+    """Blocks of a no-reference, lossless archive decoded on the device
+    (sa_decoder_*): a wave per block and chain, in a number of launches fixed
+    from the blocks' symbol counts.  SA_DEC_SLICE and SA_DEC_INFLIGHT are read
+    when the Decoder is made.  Its device and page-locked buffers are kept."""
+
+    def __init__(self, device: int = 0):
+        self._lib = load_library()
+        self._h = self._lib.sa_decoder_create(device)
+        if not self._h:
+            raise SeqArcError(f"sa_decoder_create failed: no usable gfx950 device {device}")
+
+    def close(self):
+        if self._h:
+            self._lib.sa_decoder_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def info(self) -> dict:
+        i = DecodeInfo()
+        self._lib.sa_decoder_info(self._h, C.byref(i))
+        return {n: getattr(i, n) for n, _ in i._fields_}
+
+    def decode(self, blocks, caps, cfg: Config | None = None, template: np.ndarray | None = None, long_reads=None,
+               threads: int = 4) -> list[tuple]:
+        """One sa_decode_blocks over the encoded blocks (bytes); caps[i] bounds block i's
+        arrays as decode_block's text_bytes does.  Per block (Block | None, md5_ok, status):
+        the Block is None where the status (DEC_*) is not 0."""
+        n = len(blocks)
+        cfg = cfg or Config()
+        tmpl = np.zeros(512, np.uint8) if template is None else np.ascontiguousarray(template, dtype=np.uint8)
+        srcs = [np.frombuffer(b, np.uint8) for b in blocks]
+        ins = (C.c_void_p * max(1, n))(*[_ptr(s) for s in srcs])
+        lens = np.array([s.size for s in srcs], np.uint64)
+        lng = np.array([1 if (long_reads is not None and long_reads[i]) else 0 for i in range(n)], np.int32)
+        outs = (_SaDecoded * max(1, n))()
+        keep = []
+        for i in range(n):
+            cap = int(caps[i]) + 64
+            mr = cap // 4 + 8
+            a = (np.empty(cap, np.uint8), np.empty(mr, np.uint16), np.empty(cap, np.uint8), np.empty(mr, np.int32),
+                 np.empty(cap, np.uint8))
+            keep.append(a)
+            outs[i] = _SaDecoded(_ptr(a[0]), _ptr(a[1]), _ptr(a[2]), _ptr(a[3]), _ptr(a[4]), cap, cap, mr, 0, 0)
+        status = np.zeros(max(1, n), np.uint32)
+        c = cfg._c()
+        rc = self._lib.sa_decode_blocks(self._h, ins, _ptr(lens), _ptr(lng), n, C.byref(c), _ptr(tmpl), int(threads), outs,
+                                        _ptr(status))
+        if rc < 0:
+            raise SeqArcError(f"sa_decode_blocks ({rc}): {self._lib.sa_decoder_error(self._h).decode()}")
+        res = []
+        for i in range(n):
+            st = int(status[i])
+            if st:
+                res.append((None, False, st))
+                continue
+            names, nl, seq, sl, qual = keep[i]
+            k = int(outs[i].nreads)
+            ln, ls = int(nl[:k].astype(np.int64).sum()), int(sl[:k].astype(np.int64).sum())
+            res.append((Block(names[:ln].copy(), nl[:k].copy(), seq[:ls].copy(), sl[:k].copy(), qual[:ls].copy(), int(caps[i])),
+                        bool(outs[i].md5_ok), 0))
+        return res
 
 
 class AlignChain:

@@ -12,8 +12,8 @@ LIB_DIR = os.path.join(HERE, "lib")
 LIB = os.path.join(LIB_DIR, "libseqarc_amd.so")
 BIN_DIR = os.path.join(HERE, "bin")
 CLI = os.path.join(BIN_DIR, "seqarc_amd")
-SOURCES = ["sa_engine.hip", "fastq_host.cpp", "arc_file.cpp", "arc_decode.cpp"]
-DEPS = SOURCES + ["seqarc_cli.cpp", "sa_kernels.hip", "sa_hash.hip", "sa_parse.hip", "sa_inflate.hip", "sa_inflate.h", "sa_devtext.hip", "sa_devcut.h", "sa_gunzip.hip", "sa_gunzip.h", "arc_decode_host.h", "sa_common.h", "sa_device.h", "sa_logic.h", "sa_plan.h", "sa_knobs.h", "sa_md5_lanes.h",
+SOURCES = ["sa_engine.hip", "sa_decode.hip", "fastq_host.cpp", "arc_file.cpp", "arc_decode.cpp"]
+DEPS = SOURCES + ["seqarc_cli.cpp", "sa_kernels.hip", "sa_hash.hip", "sa_parse.hip", "sa_inflate.hip", "sa_inflate.h", "sa_devtext.hip", "sa_devcut.h", "sa_gunzip.hip", "sa_gunzip.h", "sa_decoder.h", "sa_decode_logic.h", "arc_decode_host.h", "sa_common.h", "sa_device.h", "sa_logic.h", "sa_plan.h", "sa_knobs.h", "sa_md5_lanes.h",
                   "sa_align_host.h", "cli_knobs.h", "cli_plan.h", "cli_gzstream.h", "cli_devinput.h"]
 
 

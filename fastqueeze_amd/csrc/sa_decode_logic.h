@@ -60,16 +60,7 @@
 
 namespace sa {
 
-// why a block's chain ended
-enum {
-    SA_DEC_OK = 0,
-    SA_DEC_LAYOUT = 1,       // the encap walk or one of the small streams failed, or the arrays are too small
-    SA_DEC_INPUT = 2,        // a chain read past its payload
-    SA_DEC_SLOT = 3,         // the coder's slot is not below the model's total
-    SA_DEC_RANGE = 4,        // range 0 after a carry-less squeeze (the renormalisation is bounded)
-    SA_DEC_PLACE = 5,        // the side streams disagree with each other or with the qualities
-    SA_DEC_UNSUPPORTED = 6   // not decoded by these functions: -l and reference-path blocks, a block beyond the budget
-};
+// (why a block's chain ended: SA_DEC_* of include/seqarc_amd.h)
 
 constexpr uint32_t DEC_LANES = 64;
 constexpr uint32_t DEC_QSYM = 95;          // SIMPLE_MODEL<95>: symbol 94 = "the rest of the read is '#'"
@@ -495,6 +486,50 @@ inline DecPlan plan_decode(const sa_cfg& cfg, uint32_t nblocks, const DecBlockSi
         if (cap && p.inflight > cap) p.inflight = cap;
     }
     return p;
+}
+
+// ---- a block of a group (sa_decoder.h lays the groups out) ----
+// Byte offsets into the group's arena, each on a DEC_PAD boundary and checked by
+// the host against the arena's size before any launch (dec_desc_ok).
+struct DecDesc {
+    uint64_t qin, sin, lens;                          // uploaded: the two payloads, n x u32 lengths
+    uint64_t tip_off, tip_len, maxq, exc, gaps, chs;  // uploaded: the placement's side arrays
+    uint64_t Q, S;                                    // outputs: total bytes each (S is zeroed over dec_pad(total))
+    uint64_t models, tab;                             // the QUAL and SEQ tables
+    uint64_t total, ngaps, nchs;
+    uint32_t qin_len, sin_len, n, ntip;
+};
+static_assert(sizeof(DecDesc) == 144, "DecDesc is copied to the device as it is");
+
+template <class W>
+SAD_HD void dec_block_qual(W& w, uint8_t* base, const DecDesc& d, DecChain& c, int32_t qlevel, uint32_t slice, uint32_t& ev)
+{
+    dec_qual_slice(w, c, base + d.qin, d.qin_len, reinterpret_cast<const uint32_t*>(base + d.lens), d.n, base + d.Q, base + d.models,
+                   qlevel, slice, ev);
+}
+
+// The placement once the QUAL chain is over; the block's status so far (a QUAL
+// chain that has not ended after its launches is SA_DEC_STUCK).  A status ends
+// the SEQ chain before it starts.
+SAD_HD uint32_t dec_block_place(uint8_t* base, const DecDesc& d, const DecChain& qc, DecChain& sc)
+{
+    uint32_t st = qc.status ? qc.status : !qc.done ? (uint32_t)SA_DEC_STUCK : 0u;
+    if (!st)
+        st = dec_place(base + d.Q, base + d.S, d.ntip, reinterpret_cast<const uint64_t*>(base + d.tip_off),
+                       reinterpret_cast<const uint32_t*>(base + d.tip_len), base + d.maxq, reinterpret_cast<const uint64_t*>(base + d.exc),
+                       reinterpret_cast<const uint64_t*>(base + d.gaps), d.ngaps, base + d.chs, d.nchs);
+    if (st) {
+        sc.status = st;
+        sc.done = 1;
+    }
+    return st;
+}
+
+template <class W>
+SAD_HD void dec_block_seq(W& w, uint8_t* base, const DecDesc& d, DecChain& c, uint32_t mask, uint32_t slice, uint32_t& ev)
+{
+    dec_seq_slice(w, c, base + d.sin, d.sin_len, reinterpret_cast<const uint32_t*>(base + d.lens), d.n, base + d.S, base + d.tab, mask,
+                  slice, ev);
 }
 
 }  // namespace sa

@@ -33,6 +33,9 @@
 //   --gpu-gunzip     gzip inputs that are not BGZF (gzip, pigz, concatenated members) are
 //                    inflated on the first device by speculation (sa_gunzip_run); with
 //                    --gpu-text their text stays on the device too (sa_gunzip_run_dev)
+//   --gpu-decode     -d: the blocks of a no-reference, lossless archive are decoded on the
+//                    device, windows of blocks a call (sa_decode_blocks; --device N; off by
+//                    default); a block the device does not take is decoded on the host
 //
 // Compression mirrors SeqArc-1.6 main@0x41fd40 -> SeqArcContext::doReadAndEncode
 // @0x41a4e0 as a stream: one reader thread cuts 50 MiB blocks as the input
@@ -91,7 +94,8 @@ int usage()
             "                  [--block-size MiB] [--device D] [--share-device] [--ramp] [--release]\n"
             "                  [--stage-ahead] [--writers N] [--read-threads N] [--gpu-inflate] [--gpu-text]\n"
             "                  [--gpu-gunzip]\n"
-            "       seqarc_amd -d [-t N] [-f] [-p] [-P 1|2|3] [ref.fa] ARCHIVE.arc [PREFIX] [-o PREFIX]\n"
+            "       seqarc_amd -d [-t N] [-f] [-p] [-P 1|2|3] [--gpu-decode] [--device D] [ref.fa] ARCHIVE.arc [PREFIX]\n"
+            "                  [-o PREFIX]\n"
             "       seqarc_amd -i ref.fa            (HASH index: ref.fa.hash + ref.fa.md5)\n"
             "       (-s with -i / -c / -d and ref.fa: the index image in /dev/shm/<ref file name>)\n"
             "       (-c / -d with ref.fa: the reference path; -I N insert size, --maxmis M)\n"
@@ -99,7 +103,8 @@ int usage()
             "       (--gpu-text: BGZF inputs of -c are inflated, cut into blocks and parsed on the device, the text\n"
             "        never on the host; not with --ingest-only, --host-only, --host-parse, --stage-ahead)\n"
             "       (--gpu-gunzip: gzip inputs of -c that are not BGZF are inflated on the first device; with\n"
-            "        --gpu-text their text stays on the device as well)\n");
+            "        --gpu-text their text stays on the device as well)\n"
+            "       (--gpu-decode: -d decodes the blocks of a no-reference, lossless archive on the device)\n");
     return 2;
 }
 
@@ -1079,6 +1084,7 @@ struct Options : cli::PlanOpts {   // (PlanOpts, cli_plan.h: the options the bat
     const char *f1 = nullptr, *f2 = nullptr, *out = nullptr, *arc = nullptr, *ref = nullptr;
     bool compress = false, decompress = false, index = false, force = false, in_dir = false, share_device = false,
          verbose = false, release = false, shm = false, maxmis_set = false, ingest_crc = false, gpu_inflate = false, gpu_gunzip = false,
+         gpu_decode = false,   // --gpu-decode: -d hands windows of blocks to sa_decode_blocks
          gpu_text = false;   // --gpu-text: BGZF inputs inflated, cut and parsed on the device (DevInput, read_device)
     int writers = 8;        // --writers: the archive writer's copy threads (ArcWriter; 1: write(2) in order)
     int pipe = 0, device = 0, block_mib = 50, maxmis = 7;
@@ -2627,6 +2633,22 @@ int decompress(const Options& o)
     cfg.lossy = lossy ? 1.0 : 0.0;
     cfg.bin_mode = tmpl[0];
 
+    // --gpu-decode takes the blocks of a no-reference, lossless archive; any other archive runs as without the switch
+    struct GpuDec {
+        sa_decoder* h = nullptr;
+        ~GpuDec() { sa_decoder_destroy(h); }
+    } gdec;
+    if (o.gpu_decode) {
+        if (!noref || lossy) {
+            if (o.verbose)
+                fprintf(stderr, "seqarc_amd: --gpu-decode does not apply (%s): running without it\n",
+                        !noref ? "the archive was made with a reference" : "the archive was made with -l");
+        } else if (!(gdec.h = sa_decoder_create(o.device))) {
+            fprintf(stderr, "seqarc_amd: --gpu-decode: no usable gfx950 device %d\n", o.device);
+            return 1;
+        }
+    }
+
     // outputs
     FILE *o1 = nullptr, *o2 = nullptr;
     int mate = -1;
@@ -2670,23 +2692,87 @@ int decompress(const Options& o)
     };
     int rc = 0, bad_md5 = 0;
     const uint32_t nt = (uint32_t)std::max(1, o.threads > 0 ? o.threads : 1);
-    for (uint32_t b0 = 0; b0 < nblocks && !rc; b0 += nt) {
-        const uint32_t n = std::min(nt, nblocks - b0);
+    auto arrays = [&](Dec& d, const Blk& bk) {
+        const uint64_t cap = bk.text + 64;   // names, bases, qualities each fit the FASTQ text
+        d.names.resize(cap); d.seq.resize(cap); d.qual.resize(cap);
+        d.nl.resize(cap / 4 + 8); d.sl.resize(cap / 4 + 8);
+        d.d = sa_decoded{d.names.data(), d.nl.data(), d.seq.data(), d.sl.data(), d.qual.data(), cap, cap,
+                         (uint32_t)(cap / 4 + 8), 0, 0};
+    };
+    auto host_decode = [&](Dec& d, const Blk& bk) {
+        d.rc = noref ? sa_decode_block(a.data() + bk.off, bk.size, &cfg, tmpl, (int32_t)bk.lng, &d.d)
+                     : sa_decode_block_ref(a.data() + bk.off, bk.size, &cfg, tmpl, (int32_t)bk.lng, &gref, &d.d);
+    };
+    // --gpu-decode: the first window is -t blocks, the later ones the plan's blocks in flight (what the last call
+    // reported), none more than a quarter of the host's memory in output arrays
+    uint32_t win = nt;
+    const uint64_t host_cap = (uint64_t)sysconf(_SC_PHYS_PAGES) * (uint64_t)sysconf(_SC_PAGESIZE) / 4;
+    sa_decode_info gsum{};
+    for (uint32_t b0 = 0, n = 0; b0 < nblocks && !rc; b0 += n) {
+        n = std::min(nt, nblocks - b0);
+        if (gdec.h) {
+            uint64_t bytes = 0;
+            for (n = 0; b0 + n < nblocks && n < win; n++) {   // (at least one block)
+                bytes += 3 * (blks[b0 + n].text + 64);
+                if (n && bytes > host_cap) break;
+            }
+        }
         std::vector<Dec> ds(n);
-        std::vector<std::thread> th;
-        for (uint32_t i = 0; i < n; i++)
-            th.emplace_back([&, i]() {
+        std::vector<uint32_t> todo;   // the blocks host threads decode: all of them without --gpu-decode
+        if (gdec.h) {
+            std::vector<const uint8_t*> in(n);
+            std::vector<uint64_t> len(n);
+            std::vector<int32_t> lng(n);
+            std::vector<sa_decoded> outs(n);
+            std::vector<uint32_t> status(n, 0);
+            for (uint32_t i0 = 0; i0 < n; i0 += nt) {   // (the arrays' pages are touched on -t threads, as below)
+                std::vector<std::thread> th;
+                for (uint32_t i = i0; i < std::min(n, i0 + nt); i++) th.emplace_back([&, i]() { arrays(ds[i], blks[b0 + i]); });
+                for (auto& x : th) x.join();
+            }
+            for (uint32_t i = 0; i < n; i++) {
                 const Blk& bk = blks[b0 + i];
-                Dec& d = ds[i];
-                const uint64_t cap = bk.text + 64;   // names, bases, qualities each fit the FASTQ text
-                d.names.resize(cap); d.seq.resize(cap); d.qual.resize(cap);
-                d.nl.resize(cap / 4 + 8); d.sl.resize(cap / 4 + 8);
-                d.d = sa_decoded{d.names.data(), d.nl.data(), d.seq.data(), d.sl.data(), d.qual.data(), cap, cap,
-                                 (uint32_t)(cap / 4 + 8), 0, 0};
-                d.rc = noref ? sa_decode_block(a.data() + bk.off, bk.size, &cfg, tmpl, (int32_t)bk.lng, &d.d)
-                             : sa_decode_block_ref(a.data() + bk.off, bk.size, &cfg, tmpl, (int32_t)bk.lng, &gref, &d.d);
-            });
-        for (auto& x : th) x.join();
+                in[i] = a.data() + bk.off;
+                len[i] = bk.size;
+                lng[i] = (int32_t)bk.lng;
+                outs[i] = ds[i].d;
+            }
+            const int bad = sa_decode_blocks(gdec.h, in.data(), len.data(), lng.data(), n, &cfg, tmpl, (int)nt, outs.data(), status.data());
+            if (bad < 0) {
+                fprintf(stderr, "seqarc_amd: --gpu-decode: %s\n", sa_decoder_error(gdec.h));
+                rc = 1;
+                break;
+            }
+            sa_decode_info gi;
+            sa_decoder_info(gdec.h, &gi);
+            gsum.groups += gi.groups; gsum.qual_launches += gi.qual_launches; gsum.seq_launches += gi.seq_launches;
+            gsum.unsupported += gi.unsupported; gsum.inflight = std::max(gsum.inflight, gi.inflight); gsum.slice = gi.slice;
+            gsum.init_ms += gi.init_ms; gsum.qual_ms += gi.qual_ms; gsum.place_ms += gi.place_ms; gsum.seq_ms += gi.seq_ms;
+            gsum.h2d_ms += gi.h2d_ms; gsum.d2h_ms += gi.d2h_ms;
+            win = std::max(nt, gi.inflight);
+            for (uint32_t i = 0; i < n; i++) {
+                ds[i].d = outs[i];
+                ds[i].rc = status[i] ? -1 : (int64_t)outs[i].nreads;
+                if (status[i] == SA_DEC_UNSUPPORTED || status[i] == SA_DEC_STUCK) {   // the host takes the block
+                    if (o.verbose)
+                        fprintf(stderr, "seqarc_amd: --gpu-decode: block %u %s: the host decodes it\n", b0 + i,
+                                status[i] == SA_DEC_STUCK ? "did not end in its launches" : "is not supported on the device");
+                    todo.push_back(i);
+                }
+            }
+        } else {
+            for (uint32_t i = 0; i < n; i++) todo.push_back(i);
+        }
+        for (size_t k0 = 0; k0 < todo.size(); k0 += nt) {
+            std::vector<std::thread> th;
+            for (size_t k = k0; k < std::min(todo.size(), k0 + nt); k++)
+                th.emplace_back([&, k]() {
+                    Dec& d = ds[todo[k]];
+                    if (!gdec.h) arrays(d, blks[b0 + todo[k]]);
+                    host_decode(d, blks[b0 + todo[k]]);
+                });
+            for (auto& x : th) x.join();
+        }
         for (uint32_t i = 0; i < n && !rc; i++) {
             Dec& d = ds[i];
             if (d.rc < 0) { fprintf(stderr, "seqarc_amd: block %u does not decode\n", b0 + i); rc = 1; break; }
@@ -2697,6 +2783,11 @@ int decompress(const Options& o)
             write_reads(o1, o2, d.names, d.nl, d.seq, d.sl, d.qual, d.d.nreads, paired, mate, bare);
         }
     }
+    if (gdec.h && o.verbose)
+        fprintf(stderr, "seqarc_amd: sa_decode_blocks: groups %u, inflight %u, slice %u, qual_launches %u, seq_launches %u, "
+                        "unsupported %u, init_ms %.2f, qual_ms %.2f, place_ms %.2f, seq_ms %.2f, h2d_ms %.2f, d2h_ms %.2f\n",
+                gsum.groups, gsum.inflight, gsum.slice, gsum.qual_launches, gsum.seq_launches, gsum.unsupported, gsum.init_ms,
+                gsum.qual_ms, gsum.place_ms, gsum.seq_ms, gsum.h2d_ms, gsum.d2h_ms);
     if (o1 && o1 != stdout) fclose(o1);
     else if (o1) fflush(o1);
     if (o2) fclose(o2);
@@ -2749,6 +2840,7 @@ int main(int argc, char** argv)
         else if (!strcmp(a, "--gpu-inflate")) o.gpu_inflate = true;
         else if (!strcmp(a, "--gpu-gunzip")) o.gpu_gunzip = true;
         else if (!strcmp(a, "--gpu-text")) o.gpu_text = true;
+        else if (!strcmp(a, "--gpu-decode")) o.gpu_decode = true;
         else if (!strcmp(a, "--read-threads")) { if (!ival(o.read_threads, 0)) return usage(); }
         else if (!strcmp(a, "--writers")) { if (!ival(o.writers, 1)) return usage(); }
         else if (!strcmp(a, "--no-ramp")) o.ramp = false;

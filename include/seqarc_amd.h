@@ -326,6 +326,37 @@ typedef struct {
 int64_t sa_decode_block_ref(const uint8_t *in, uint64_t len, const sa_cfg *cfg, const uint8_t tmpl[512],
                             int32_t long_reads, const sa_ref *ref, sa_decoded *out);
 
+/* ---- block decoder on the device (no-reference, lossless archives) --------- */
+/* Why a block's decode ended (fastqueeze_amd/csrc/sa_decode_logic.h, sa_decoder.h). */
+enum {
+    SA_DEC_OK = 0,
+    SA_DEC_LAYOUT = 1,       /* the encap walk or one of the small streams failed, or the arrays are too small */
+    SA_DEC_INPUT = 2,        /* a chain read past its payload */
+    SA_DEC_SLOT = 3,         /* the coder's slot is not below the model's total */
+    SA_DEC_RANGE = 4,        /* range 0 after a carry-less squeeze (the renormalisation is bounded) */
+    SA_DEC_PLACE = 5,        /* the side streams disagree with each other or with the qualities */
+    SA_DEC_UNSUPPORTED = 6,  /* not decoded on the device: -l blocks, a block beyond the memory budget */
+    SA_DEC_STUCK = 7         /* a chain had not ended after the launches its symbol count allows */
+};
+/* Many blocks at once, a wave per block and chain (sa_decode.hip): the QUAL and SEQ chains run
+ * in launches of SA_DEC_SLICE symbols (default 2^18), a number of launches fixed before the first
+ * one from the blocks' symbol counts; at most SA_DEC_INFLIGHT blocks (default: what 7/8 of the
+ * device's free memory holds) are on the device at a time.  Both are read at sa_decoder_create. */
+typedef struct sa_decoder sa_decoder;
+sa_decoder *sa_decoder_create(int device);      /* own stream; no sa_ctx needed */
+void sa_decoder_destroy(sa_decoder *);
+const char *sa_decoder_error(const sa_decoder *);
+/* n blocks of one no-reference archive: in[i]/len[i]/long_reads[i] as for sa_decode_block, out[i] caller-owned
+ * as for sa_decode_block.  status[i]: SA_DEC_*.  threads: host threads for the pre-pass and MD5.
+ * Returns the number of blocks whose status != 0, or <0 for a call error.  A block with a status has
+ * undefined out[i] contents; the caller may hand it to sa_decode_block. */
+int sa_decode_blocks(sa_decoder *, const uint8_t *const *in, const uint64_t *len, const int32_t *long_reads,
+                     uint32_t n, const sa_cfg *cfg, const uint8_t tmpl[512], int threads,
+                     sa_decoded *out, uint32_t *status);
+typedef struct { uint32_t groups, inflight, slice, qual_launches, seq_launches, unsupported;
+                 float init_ms, qual_ms, place_ms, seq_ms, h2d_ms, d2h_ms; } sa_decode_info;
+void sa_decoder_info(const sa_decoder *, sa_decode_info *);   /* the last call */
+
 /* RFC 1321 MD5 (MD5File@0x405950 of the reference FASTA, the block digests) */
 void sa_md5(const uint8_t *data, uint64_t len, uint8_t digest[16]);
 
